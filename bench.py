@@ -8,7 +8,11 @@ patch-graph index build -> 2-level correlation -> neighbors -> fastba.BA(iterati
 The Update network is replaced by fixed delta / weight tensors.  All inputs are resident in HBM before
 the timed region.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+A plain run sets up, settles the clocks, runs W warm-up steps, times exactly K steps and prints the headline line.
+--dump-outputs DIR writes what the last timed step handed its caller as DIR/<name>.npy (see dump_outputs).
+--full adds everything else the line has carried: more timed windows, the correlation roofline, per-stage times, the
+drop-in call sequence, the stress / stream sub-records, the CPU port and the closed-loop ATE against the oracle.
 N > 1: either launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...` (the ranks
 read RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment) or run plainly -- then this process starts the N
 rank processes itself, before it touches any GPU, and exits with their status.  Every rank runs an independent
@@ -164,6 +168,39 @@ def cpu_baseline(st, max_seconds=30.0, gpu_poses=None):
     }
 
 
+DUMP_CORR_EDGES = 8192          # 8,192 of the E rows of the correlation (882 values each): 28.9 MB in float32
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, out, up, seed=0):
+    """What a caller of UpdatePath.step() holds after the last timed step: the step's return value (coords, corr,
+    ix, jx) and the poses / patches the bundle adjustment updated in place, as <path>/<name>.npy in float32 (float64 for
+    the int64 neighbor lists).  All E rows of the correlation in float32 would be 168 MB: a fixed seeded sample of
+    edges is written instead (`corr_sample`, its edge ids in `corr_sample_edges`).  Must be called before any further
+    step: coords / corr / ix / jx live in buffers the next step overwrites."""
+    import numpy as np
+    import torch
+    torch.cuda.synchronize()
+    arrays = {"poses": up.poses, "patches": up.patches}
+    arrays.update(out)
+    if "corr" in arrays:
+        corr = arrays.pop("corr").reshape(-1, 882)
+        rows = np.sort(np.random.default_rng(seed).choice(len(corr), min(len(corr), DUMP_CORR_EDGES), replace=False))
+        arrays["corr_sample"] = corr[torch.as_tensor(rows, device=corr.device)]
+        arrays["corr_sample_edges"] = torch.as_tensor(rows)
+    res = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        res[name] = a.astype(np.float64) if a.dtype.kind in "iu" else a.astype(np.float32)
+    total = sum(a.nbytes for a in res.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes, more than the %d allowed" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for name, a in res.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return sorted(res)
+
+
 def dry_run(args):
     """the N-rank plumbing of main() without a GPU: same group calls, a trivial step"""
     import numpy as np
@@ -249,9 +286,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--windows", type=int, default=5, help="timed windows of K steps each; the median window is reported")
+    ap.add_argument("--full", action="store_true", help="after the headline, everything else the line reports: more timed "
+                    "windows, roofline, stage times, drop-in, stress / stream sub-records, CPU port, ATE against the oracle")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--windows", type=int, default=5, help="with --full: timed windows of K steps each, the headline's the "
+                    "first; all of them and their median in `timed_windows`")
     ap.add_argument("--config", default="default", help="synthetic workload (default | stress | init | pr1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU port and the ATE record")
     ap.add_argument("--settle-ms", type=float, default=300.0, help="untimed clock-settling load before the warm-up steps")
     ap.add_argument("--graph", action="store_true", help="replay the ~20 launches of a step as one captured hipGraph "
                     "(default: eager launches on one stream; measured to run at the same rate)")
@@ -259,15 +300,14 @@ def main():
     ap.add_argument("--overlap", action="store_true", help="build the patch-graph index on a side stream under the "
                     "correlation (measured: no gain, the dispatcher does not interleave the small kernels)")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
-    ap.add_argument("--no-dropin", action="store_true", help="skip timing the reference-shaped drop-in call sequence")
-    ap.add_argument("--no-extra", action="store_true", help="skip the stress-configuration and stream sub-records")
+    ap.add_argument("--no-dropin", action="store_true", help="with --full: skip timing the reference-shaped drop-in call sequence")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the stress-configuration and stream sub-records")
     ap.add_argument("--dry-run", action="store_true", help="no GPU: the launch / rendezvous / gather plumbing only, on "
                     "gloo with a trivial step (tests/test_replicas_gloo.py); the line says dry_run and is not a measurement")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(spawn_ranks(args.gpus, sys.argv[1:]))
 
-    import numpy as np
     import torch
 
     from cdv_slam_amd import synth
@@ -315,22 +355,92 @@ def main():
 
     if dbg:
         print("debug: corr event ms after settle: %.5f" % corr_event_ms(up, 50), file=sys.stderr, flush=True)
+    # the settling ran for a time, not a count of steps: back to the initial poses / patches so that the W + K steps after
+    # it see the same inputs in every run (--dump-outputs compares runs output for output)
+    up.reset()
     for _ in range(args.warmup):
         run_step()
-    # `--windows` timed windows of EXACTLY K steps each, every one bracketed by barrier + synchronise on both sides and
-    # reduced with MAX over the ranks; the line reports the MEDIAN window (SURVEY 8(d) asks for a median) and lists all of them
-    windows = []
-    ev_head0 = up.graph.events.counts()
-    for _ in range(max(1, args.windows)):
+
+    def timed_window():
+        """EXACTLY K steps, bracketed by barrier + synchronise on both sides, reduced with MAX over the ranks"""
         grp.barrier()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            run_step()
+            out = run_step()
         grp.barrier()
-        windows.append(grp.max_over_ranks(time.perf_counter() - t0))
-    elapsed_max = float(np.median(windows))
-    elapsed = elapsed_max
+        return grp.max_over_ranks(time.perf_counter() - t0), out
+
+    ev_head0 = up.graph.events.counts()
+    elapsed_max, last_out = timed_window()
     ev_head = events_since(up.graph.events, ev_head0)
+    checksum = float(up.poses.double().abs().sum().item())
+    dumped = dump_outputs(args.dump_outputs, last_out, up) if args.dump_outputs and rank == 0 else None
+    del last_out
+    full = run_full(args, grp, st, up, dev, timed_window, elapsed_max, ev_head, events_since, dbg) if args.full else {}
+
+    # ---- gather per-rank metrics: [pose checksum, fps] (trajectory-metric gather of SURVEY.md 8(e)) ---
+    per_rank = grp.gather_metrics([checksum, args.steps / elapsed_max])
+    if len(per_rank) != args.gpus:
+        raise SystemExit("gathered %d rows, --gpus says %d" % (len(per_rank), args.gpus))
+
+    if rank == 0:
+        res = {
+            "metric": "frames/sec per GPU (CDVO update, 96 patches, win=10); ATE vs ref",
+            # (a window in which a bundle adjustment was skipped or not applied measured less than an update: no number then)
+            "value": aggregate_rate(args.steps, elapsed_max, world) if not any(ev_head) else None,
+            "ba_events": ev_head,
+            "ba_events_what": "failure events counted by the BA kernels during the timed window, per path (ops.BA_EVENTS order: not "
+                              "positive definite, U_max exceeded, hand-off lost, index in its error state); every sub-record carries "
+                              "its own; a non-zero entry nulls that record's value",
+            "unit": "frames/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "settle_ms": args.settle_ms,
+            "ms_per_step": 1e3 * elapsed_max / args.steps,
+            "rccl_ranks": world if world > 1 else None,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f32",
+            "dtype_detail": "f32 arithmetic throughout (MFMA accumulate, geometry, BA); feature maps, patch tiles and the "
+                            "correlation output are stored as f16 like the reference's",
+            "data": "synthetic",
+            "config": {
+                "workload": "%s: SLAM.update hot path on a synthetic 512x384 stream, M=%d patches/frame, "
+                            "OPTIMIZATION_WINDOW=%d, E=%d edges, %d free poses; ingest+reproject+graph index+"
+                            "2-level corr+neighbors+BA(2 it); one independent sequence per GPU"
+                            % (st.cfg.name, st.cfg.M, st.cfg.opt_window, st.E, st.n - st.t0),
+                "edges": st.E, "patches_per_frame": st.cfg.M, "window": st.cfg.opt_window,
+                "launch": "hipGraph replay" if use_graph else "eager launches",
+            },
+            "per_rank": per_rank,
+            "per_rank_summary": summarise(per_rank),
+        }
+        if dumped is not None:
+            res["outputs_dumped"] = dumped
+        res.update(full)
+        print(json.dumps(res))
+    grp.close()
+
+
+def run_full(args, grp, st, up, dev, timed_window, elapsed_max, ev_head, events_since, dbg):
+    """--full: what the line reports besides the headline, measured after the headline's timed window"""
+    import numpy as np
+    import torch
+
+    from cdv_slam_amd import synth
+    from cdv_slam_amd.update import UpdatePath
+
+    world = grp.world
+
+    # `--windows` - 1 more timed windows like the headline's; SURVEY 8(d) asks for a median, reported next to all of them
+    windows = [elapsed_max]
+    ev_win0 = up.graph.events.counts()
+    for _ in range(max(1, args.windows) - 1):
+        windows.append(timed_window()[0])
+    # the events of every window, the headline's included: a non-zero entry nulls the median as it nulls `value`
+    ev_win = [a + b for a, b in zip(ev_head, events_since(up.graph.events, ev_win0))]
 
     # ---- dominant kernel (fused correlation): HIP events around its launch inside full steps ----------
     # (event pairs recorded back to back in a stream of full steps and read after ONE synchronisation at the end: a host
@@ -541,98 +651,61 @@ def main():
         except Exception as ex:
             extra["stream_fps"] = {"error": repr(ex)}
 
-    # ---- gather per-rank metrics: [pose checksum, fps] (trajectory-metric gather of SURVEY.md 8(e)) ---
-    per_rank = grp.gather_metrics([float(up.poses.double().abs().sum().item()), args.steps / elapsed])
-    if len(per_rank) != args.gpus:
-        raise SystemExit("gathered %d rows, --gpus says %d" % (len(per_rank), args.gpus))
-
-    if rank == 0:
-        traffic, pmc = None, {}
-        tpath = os.path.join(ROOT, "profiles", "corr_traffic.json")
-        if os.path.exists(tpath):
-            try:
-                pmc = json.load(open(tpath)).get(args.config, {})
-                traffic = pmc.get("hbm_bytes_per_launch")
-            except Exception:
-                traffic, pmc = None, {}
-        # second bound of the same kernel: vector-instruction issue.  Wave-instructions per launch from the PMC pass
-        # (SQ_INSTS_VALU, profiles/corr_traffic.json) over the launch time measured above, against one VALU
-        # wave-instruction per 4 cycles per SIMD (the issue cost of the guide's cycle table; 1,024 SIMDs at 2.4 GHz)
-        valu = pmc.get("valu_insts_per_launch")
-        roofline_valu = None
-        if valu:
-            a_v = valu / (corr_ms * 1e-3) / 1e9
-            roofline_valu = {"bound": "valu_issue", "achieved": a_v, "peak": VALU_ISSUE_PEAK_GINST, "unit": "G wave-instr/s",
-                             "frac": a_v / VALU_ISSUE_PEAK_GINST, "kernel": "corr_fused2_kernel<24, 2>",
-                             "insts_per_launch": valu, "avg_launch_ms": corr_ms,
-                             "source": "SQ_INSTS_VALU of profiles/%s_corr_pmc_%s.txt" % (pmc.get("round", "r2"), args.config)}
-        res = {
-            "metric": "frames/sec per GPU (CDVO update, 96 patches, win=10); ATE vs ref",
-            # (a window in which a bundle adjustment was skipped or not applied measured less than an update: no number then)
-            "value": aggregate_rate(args.steps, elapsed_max, world) if not any(ev_head) else None,
-            "ba_events": ev_head,
-            "ba_events_what": "failure events counted by the BA kernels during the timed windows, per path (ops.BA_EVENTS order: not "
-                              "positive definite, U_max exceeded, hand-off lost, index in its error state); every sub-record carries "
-                              "its own; a non-zero entry nulls that record's value",
-            "unit": "frames/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "settle_ms": args.settle_ms,
-            "ms_per_step": 1e3 * elapsed_max / args.steps,
-            "timed_windows": {"count": len(windows), "steps_each": args.steps, "reported": "median",
-                              "ms_per_step": [1e3 * w / args.steps for w in windows]},
-            "rccl_ranks": world if world > 1 else None,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "dtype_detail": "f32 arithmetic throughout (MFMA accumulate, geometry, BA); feature maps, patch tiles and the "
-                            "correlation output are stored as f16 like the reference's",
-            "data": "synthetic",
-            "config": {
-                "workload": "%s: SLAM.update hot path on a synthetic 512x384 stream, M=%d patches/frame, "
-                            "OPTIMIZATION_WINDOW=%d, E=%d edges, %d free poses; ingest+reproject+graph index+"
-                            "2-level corr+neighbors+BA(2 it); one independent sequence per GPU"
-                            % (st.cfg.name, st.cfg.M, st.cfg.opt_window, st.E, st.n - st.t0),
-                "edges": st.E, "patches_per_frame": st.cfg.M, "window": st.cfg.opt_window,
-                "launch": "hipGraph replay" if use_graph else "eager launches",
-            },
-            "roofline": {
-                "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                "traffic_source": (None if traffic is None else "NOT measured in this run: FETCH_SIZE (x2, gfx950) + WRITE_SIZE per "
-                                   "launch from separate rocprofv3 --pmc passes of the same workload, profiles/corr_traffic.json (%s)"
-                                   % pmc.get("round", "r2")),
-                "kernel": "corr_fused2_kernel<24, 2, stream>", "avg_launch_ms": corr_ms, "algorithmic_bytes": corr_bytes,
-                "launches_per_event_pair": CORR_LAUNCHES_PER_PAIR,
-                "avg_launch_ms_single_launch_pair": corr_ms_single,
-                "frac_single_launch_pair": corr_bytes / (corr_ms_single * 1e-3) / 1e9 / HBM_PEAK_GBS,
-            },
-            "roofline_valu": roofline_valu,
-            "stages_us": stages,
-            "dropin_fps": dropin,
-            "stress": extra.get("stress"),
-            "stream_fps": extra.get("stream_fps"),
-            "per_rank": per_rank,
-            "per_rank_summary": summarise(per_rank),
-        }
-        if not args.no_cpu_baseline and world == 1:   # the CPU port is timed next to the single-GPU number only
-            up.reset()
-            up.step()
-            torch.cuda.synchronize()
-            res["cpu_baseline"] = cpu_baseline(st, args.cpu_seconds, gpu_poses=up.poses.cpu().numpy())
-            one = res["cpu_baseline"].pop("ate_vs_oracle")
-            try:
-                res["ate_vs_oracle"] = closed_loop_ate(dev, progress=lambda m: print(m, file=sys.stderr, flush=True))
-                res["ate_vs_oracle"]["one_update_at_benchmark_size"] = one
-            except Exception as ex:
-                res["ate_vs_oracle"] = {"error": repr(ex), "one_update_at_benchmark_size": one}
-        else:
-            res["cpu_baseline"] = None
-            res["ate_vs_oracle"] = None
-        print(json.dumps(res))
-    grp.close()
+    traffic, pmc = None, {}
+    tpath = os.path.join(ROOT, "profiles", "corr_traffic.json")
+    if os.path.exists(tpath):
+        try:
+            pmc = json.load(open(tpath)).get(args.config, {})
+            traffic = pmc.get("hbm_bytes_per_launch")
+        except Exception:
+            traffic, pmc = None, {}
+    # second bound of the same kernel: vector-instruction issue.  Wave-instructions per launch from the PMC pass
+    # (SQ_INSTS_VALU, profiles/corr_traffic.json) over the launch time measured above, against one VALU
+    # wave-instruction per 4 cycles per SIMD (the issue cost of the guide's cycle table; 1,024 SIMDs at 2.4 GHz)
+    valu = pmc.get("valu_insts_per_launch")
+    roofline_valu = None
+    if valu:
+        a_v = valu / (corr_ms * 1e-3) / 1e9
+        roofline_valu = {"bound": "valu_issue", "achieved": a_v, "peak": VALU_ISSUE_PEAK_GINST, "unit": "G wave-instr/s",
+                         "frac": a_v / VALU_ISSUE_PEAK_GINST, "kernel": "corr_fused2_kernel<24, 2>",
+                         "insts_per_launch": valu, "avg_launch_ms": corr_ms,
+                         "source": "SQ_INSTS_VALU of profiles/%s_corr_pmc_%s.txt" % (pmc.get("round", "r2"), args.config)}
+    res = {
+        "timed_windows": {"count": len(windows), "steps_each": args.steps, "headline": "the first window",
+                          "median_ms_per_step": 1e3 * float(np.median(windows)) / args.steps if not any(ev_win) else None,
+                          "ms_per_step": [1e3 * w / args.steps for w in windows], "ba_events": ev_win},
+        "roofline": {
+            "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+            "traffic_source": (None if traffic is None else "NOT measured in this run: FETCH_SIZE (x2, gfx950) + WRITE_SIZE per "
+                               "launch from separate rocprofv3 --pmc passes of the same workload, profiles/corr_traffic.json (%s)"
+                               % pmc.get("round", "r2")),
+            "kernel": "corr_fused2_kernel<24, 2, stream>", "avg_launch_ms": corr_ms, "algorithmic_bytes": corr_bytes,
+            "launches_per_event_pair": CORR_LAUNCHES_PER_PAIR,
+            "avg_launch_ms_single_launch_pair": corr_ms_single,
+            "frac_single_launch_pair": corr_bytes / (corr_ms_single * 1e-3) / 1e9 / HBM_PEAK_GBS,
+        },
+        "roofline_valu": roofline_valu,
+        "stages_us": stages,
+        "dropin_fps": dropin,
+        "stress": extra.get("stress"),
+        "stream_fps": extra.get("stream_fps"),
+    }
+    if not args.no_cpu_baseline and world == 1:   # the CPU port is timed next to the single-GPU number only
+        up.reset()
+        up.step()
+        torch.cuda.synchronize()
+        res["cpu_baseline"] = cpu_baseline(st, args.cpu_seconds, gpu_poses=up.poses.cpu().numpy())
+        one = res["cpu_baseline"].pop("ate_vs_oracle")
+        try:
+            res["ate_vs_oracle"] = closed_loop_ate(dev, progress=lambda m: print(m, file=sys.stderr, flush=True))
+            res["ate_vs_oracle"]["one_update_at_benchmark_size"] = one
+        except Exception as ex:
+            res["ate_vs_oracle"] = {"error": repr(ex), "one_update_at_benchmark_size": one}
+    else:
+        res["cpu_baseline"] = None
+        res["ate_vs_oracle"] = None
+    return res
 
 
 if __name__ == "__main__":

@@ -13,7 +13,7 @@ echo "pytest rc=$rc"; tail -n 8 $out/${tag}_pytest.log
 if [ $rc -gt 1 ]; then echo "pytest was killed or errored out: no further GPU step"; exit $rc; fi
 unset CDV_TEST_LOG
 for cfg in default stress; do
-  timeout -k 10 400 python bench.py --steps 200 --warmup 20 --config $cfg > $out/${tag}_bench_$cfg.json 2> $out/${tag}_bench_$cfg.err
+  timeout -k 10 400 python bench.py --full --steps 200 --warmup 20 --config $cfg > $out/${tag}_bench_$cfg.json 2> $out/${tag}_bench_$cfg.err
   brc=$?
   echo "bench $cfg rc=$brc"; tail -c 1800 $out/${tag}_bench_$cfg.json; tail -n 3 $out/${tag}_bench_$cfg.err
   if [ $brc -ne 0 ]; then exit $brc; fi

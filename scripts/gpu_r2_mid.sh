@@ -11,7 +11,7 @@ rc=$?
 echo "pytest rc=$rc"; tail -n 8 $out/${tag}_pytest.log
 if [ $rc -gt 1 ]; then exit $rc; fi
 unset CDV_TEST_LOG
-timeout -k 10 300 python bench.py --steps 200 --warmup 20 --config stress --no-cpu-baseline --no-dropin > $out/${tag}_bench.json 2> $out/${tag}_bench.err
+timeout -k 10 300 python bench.py --full --steps 200 --warmup 20 --config stress --no-cpu-baseline --no-dropin > $out/${tag}_bench.json 2> $out/${tag}_bench.err
 brc=$?
 echo "bench rc=$brc"; python -c "
 import json

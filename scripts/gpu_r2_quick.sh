@@ -9,7 +9,7 @@ timeout -k 10 900 python -m pytest tests -m gpu -v --timeout 600 -p no:cacheprov
 rc=$?
 echo "pytest rc=$rc"; tail -n 6 $out/${tag}_pytest.log
 if [ $rc -gt 1 ]; then exit $rc; fi
-timeout -k 10 300 python bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-dropin > $out/${tag}_bench.json 2> $out/${tag}_bench.err
+timeout -k 10 300 python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-dropin > $out/${tag}_bench.json 2> $out/${tag}_bench.err
 brc=$?
 echo "bench rc=$brc"; python -c "
 import json

@@ -16,7 +16,7 @@ fi
 rc=$?
 echo "pytest rc=$rc"; tail -n 15 $out/${tag}_pytest.log
 if [ $rc -gt 1 ]; then echo "pytest was killed or errored out: no further GPU step"; exit $rc; fi
-timeout -k 10 400 python bench.py --steps 200 --warmup 20 > $out/${tag}_bench.json 2> $out/${tag}_bench.err
+timeout -k 10 400 python bench.py --full --steps 200 --warmup 20 > $out/${tag}_bench.json 2> $out/${tag}_bench.err
 brc=$?
 echo "bench rc=$brc"; tail -c 1500 $out/${tag}_bench.json; tail -n 5 $out/${tag}_bench.err
 if [ $brc -ne 0 ]; then exit $brc; fi

@@ -9,7 +9,7 @@ for v in "$@"; do
   name=${v%%:*}; envs=${v#*:}
   (
     IFS=','; for kv in $envs; do [ -n "$kv" ] && export "$kv"; done; unset IFS
-    timeout -k 10 300 python bench.py --steps 400 --warmup 20 --config $cfg --no-cpu-baseline --no-dropin --no-extra > $out/${tag}_${name}_bench.json 2> $out/${tag}_${name}_bench.err
+    timeout -k 10 300 python bench.py --full --steps 400 --warmup 20 --config $cfg --no-cpu-baseline --no-dropin --no-extra > $out/${tag}_${name}_bench.json 2> $out/${tag}_${name}_bench.err
     echo "[$name] bench rc=$?"; python - <<PY
 import json
 d=json.load(open("$out/${tag}_${name}_bench.json"))

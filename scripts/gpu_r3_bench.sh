@@ -3,7 +3,7 @@
 tag=$1; shift
 out=gpurun_out; mkdir -p $out; export TMPDIR=/tmp
 for cfg in "${@:-default}"; do
-  timeout -k 10 500 python bench.py --steps 200 --warmup 20 --config $cfg > $out/${tag}_bench_$cfg.json 2> $out/${tag}_bench_$cfg.err
+  timeout -k 10 500 python bench.py --full --steps 200 --warmup 20 --config $cfg > $out/${tag}_bench_$cfg.json 2> $out/${tag}_bench_$cfg.err
   echo "bench $cfg rc=$?"; python - <<PY
 import json
 d=json.load(open("$out/${tag}_bench_$cfg.json"))

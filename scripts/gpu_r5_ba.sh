@@ -10,6 +10,6 @@ cat $out/${tag}_stamps_default.log
 rm -f $out/${tag}_variants.log
 for i in 1 2; do timeout -k 10 200 python scripts/exp_variants.py default stress >> $out/${tag}_variants.log 2>&1 || exit 1; done
 grep -v amdgpu.ids $out/${tag}_variants.log
-timeout -k 10 300 python bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-dropin --no-extra > $out/${tag}_bench.json 2> $out/${tag}_bench.err || exit 1
+timeout -k 10 300 python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-dropin --no-extra > $out/${tag}_bench.json 2> $out/${tag}_bench.err || exit 1
 python -c "
 import json;r=json.loads(open('$out/${tag}_bench.json').read().strip().split('\n')[-1]);print('bench', r['value'], r['ms_per_step'], r['stages_us'])"

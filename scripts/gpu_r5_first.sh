@@ -10,7 +10,7 @@ timeout -k 10 1000 python -m pytest tests -m gpu -v --timeout 600 -p no:cachepro
 rc=$?
 echo "pytest rc=$rc"; grep -E "FAILED|ERROR|passed|failed" $out/${tag}_pytest.log | tail -n 25
 if [ $rc -gt 1 ]; then echo "pytest was killed or errored out: no further GPU step"; exit $rc; fi
-timeout -k 10 600 python bench.py --steps 200 --warmup 20 > $out/${tag}_bench.json 2> $out/${tag}_bench.err
+timeout -k 10 600 python bench.py --full --steps 200 --warmup 20 > $out/${tag}_bench.json 2> $out/${tag}_bench.err
 brc=$?
 echo "bench rc=$brc"; tail -c 600 $out/${tag}_bench.json; echo; tail -n 8 $out/${tag}_bench.err
 if [ $brc -ne 0 ]; then exit $brc; fi
