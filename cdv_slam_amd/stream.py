@@ -10,7 +10,7 @@ pieces together (edge counts change every frame, buffers wrap around their rings
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, synth
 from .edges import EdgeStore, frames_keyframe_shift
 
 
@@ -18,12 +18,13 @@ class StreamRunner:
     def __init__(self, device, M=96, ht=384, wd=512, C=24, mem=36, pmem=36, buffer_size=512, patch_lifetime=13,
                  removal_window=22, opt_window=10, keyframe_index=4, seed=1234, loop_closure=False, max_edge_age=1000,
                  global_opt_freq=15, backend_thresh=64.0, pose_init=None, record_global=False, keyframe_thresh=12.5, gain=0.01,
-                 pose_step=0.05):
+                 pose_step=0.05, intrinsics=None):
         """loop_closure: the LOOP_CLOSURE configuration of the reference (default_cdvslam.yaml): the patch ring holds
         MAX_EDGE_AGE frames (slam.py:66-68), proximity loop edges are added every GLOBAL_OPT_FREQ frames
         (slam.py:699-705, patchgraph.py:71-97), edges that close loops survive the removal window (slam.py:453-457) and an
         update with long-range edges runs the GLOBAL bundle adjustment over inactive + active edges (slam.py:460-478,507).
-        pose_init(n) -> 7 floats: the initial guess of frame n's pose (default: the previous pose moved forward)."""
+        pose_init(n) -> 7 floats: the initial guess of frame n's pose (default: the previous pose moved forward).
+        intrinsics: (fx, fy, cx, cy) of the camera in image pixels (before the division by RES = 4); default synth.default_intrinsics."""
         self.dev = device
         self.lc, self.max_edge_age, self.gof, self.backend_thresh = loop_closure, max_edge_age, global_opt_freq, backend_thresh
         self.last_global_ba = -1000
@@ -45,7 +46,7 @@ class StreamRunner:
         f32 = dict(dtype=torch.float32, device=device)
         self.poses = torch.zeros((self.N, 7), **f32); self.poses[:, 6] = 1.0
         self.patches = torch.zeros((self.N * M, 3, 3, 3), **f32)
-        intr = torch.tensor([wd / 2.0, wd / 2.0, wd / 2.0, ht / 2.0]) / 4.0
+        intr = torch.tensor(synth.default_intrinsics(ht, wd) if intrinsics is None else intrinsics) / 4.0
         self.intrinsics = intr.to(device).repeat(self.N, 1).contiguous()
         self.ix = torch.arange(self.N, device=device).repeat_interleave(M)
         self.fmap1 = ops.alloc_fmap_ring(mem, C, self.h, self.w, device)
@@ -241,7 +242,8 @@ class DeviceStreamRunner:
     too, patchgraph.py:71-97)."""
 
     def __init__(self, device, M=96, ht=384, wd=512, C=24, mem=36, pmem=36, buffer_size=512, patch_lifetime=13,
-                 removal_window=22, opt_window=10, keyframe_index=4, seed=1234, keyframe_thresh=12.5, gain=0.01, pose_step=0.05):
+                 removal_window=22, opt_window=10, keyframe_index=4, seed=1234, keyframe_thresh=12.5, gain=0.01, pose_step=0.05,
+                 intrinsics=None):
         import ctypes
         from . import _lib
         self.pose_step = pose_step
@@ -256,7 +258,7 @@ class DeviceStreamRunner:
         f32 = dict(dtype=torch.float32, device=device)
         self.poses = torch.zeros((self.N, 7), **f32); self.poses[:, 6] = 1.0
         self.patches = torch.zeros((self.N * M, 3, 3, 3), **f32)
-        intr = torch.tensor([wd / 2.0, wd / 2.0, wd / 2.0, ht / 2.0]) / 4.0
+        intr = torch.tensor(synth.default_intrinsics(ht, wd) if intrinsics is None else intrinsics) / 4.0
         self.intrinsics = intr.to(device).repeat(self.N, 1).contiguous()
         self.ix = torch.arange(self.N, device=device).repeat_interleave(M)
         self.points = torch.zeros((self.N * M, 3), **f32)

@@ -28,6 +28,13 @@ class GraphConfig:
     buffer_size: int = 64       # BUFFER_SIZE (4096 in the reference; only rows < frames are touched)
     fully_connected: bool = False  # PR1 graph: every patch to every frame (incl. self)
     seed: int = 1234
+    intr: tuple = None          # (fx, fy, cx, cy) in image pixels, before the division by RES; None: (wd/2, wd/2, wd/2, ht/2)
+
+
+# camera intrinsics of the reference's datasets, in image pixels: TartanAir (cdvslam/slam.py's 480x640 default, symmetric)
+# and EuRoC (calib/euroc.txt: no two of fx, fy, cx, cy equal, cx and cy off the image centre)
+TARTAN_INTR = (320.0, 320.0, 320.0, 240.0)
+EUROC_INTR = (458.654, 457.296, 367.215, 248.375)
 
 
 CONFIGS = {
@@ -51,7 +58,17 @@ CONFIGS = {
     # the global BA at the reference's scale (slam.py:460-478 with MAX_EDGE_AGE = 1000): N = 299 free poses, full-size
     # frames, 96 patches per frame -> U = 28,800 patches, E = 0.7 M edges
     "global_xl": GraphConfig(name="global_xl", frames=300, buffer_size=304, removal_window=10 ** 6, opt_window=10 ** 6),
+    # the reference's own camera geometries at the benchmark graph (E = 47,712): TartanAir 480x640 (maps 120x160 / 30x40)
+    # and EuRoC 480x752 (stream.py crops to multiples of 16; maps 120x188 / 30x47, an odd level-1 width) with its
+    # asymmetric calibration, the LOOP_CLOSURE patch ring (pmem = MAX_EDGE_AGE = 1000) and the reference's BUFFER_SIZE
+    "tartan": GraphConfig(name="tartan", frames=40, ht=480, wd=640, intr=TARTAN_INTR),
+    "euroc": GraphConfig(name="euroc", frames=40, ht=480, wd=752, intr=EUROC_INTR, pmem=1000, buffer_size=4096),
 }
+
+
+def default_intrinsics(ht, wd):
+    """(fx, fy, cx, cy) in image pixels of the synthetic states and streams when no calibration is given"""
+    return (wd / 2.0, wd / 2.0, wd / 2.0, ht / 2.0)
 
 
 def replay_edges(cfg: GraphConfig):
@@ -192,7 +209,7 @@ def make_state(cfg="default", features=True, **overrides) -> SynthState:
         q /= np.linalg.norm(q)
         poses[f, :3], poses[f, 3:] = t, q
 
-    intr = np.array([cfg.wd / 2.0, cfg.wd / 2.0, cfg.wd / 2.0, cfg.ht / 2.0]) / cfg.res
+    intr = np.array(default_intrinsics(cfg.ht, cfg.wd) if cfg.intr is None else cfg.intr, np.float64) / cfg.res
     intrinsics = np.tile(intr, (cfg.buffer_size, 1))
 
     centres = np.stack([rng.uniform(8, w - 8, cfg.buffer_size * M), rng.uniform(8, h - 8, cfg.buffer_size * M)], -1)

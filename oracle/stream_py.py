@@ -46,7 +46,8 @@ def flow_mag(poses, patches, intrinsics, ii, jj, kk, beta, dtype=np.float32):
 
 class StreamOracle:
     def __init__(self, M=96, ht=384, wd=512, C=24, mem=36, pmem=36, buffer_size=512, patch_lifetime=13, removal_window=22,
-                 opt_window=10, keyframe_index=4, keyframe_thresh=12.5, corr_mode="ref", dtype=np.float32, gain=0.01, pose_step=0.05):
+                 opt_window=10, keyframe_index=4, keyframe_thresh=12.5, corr_mode="ref", dtype=np.float32, gain=0.01, pose_step=0.05,
+                 intrinsics=None):
         self.pose_step = pose_step
         self.M, self.C, self.mem, self.pmem, self.N = M, C, mem, pmem, buffer_size
         self.h, self.w = ht // 4, wd // 4
@@ -54,7 +55,8 @@ class StreamOracle:
         self.corr_mode, self.dtype, self.gain = corr_mode, dtype, gain
         self.poses = np.zeros((self.N, 7), np.float32); self.poses[:, 6] = 1.0
         self.patches = np.zeros((self.N * M, 3, 3, 3), np.float32)
-        self.intrinsics = np.tile(np.array([wd / 2.0, wd / 2.0, wd / 2.0, ht / 2.0], np.float32) / 4.0, (self.N, 1))
+        intr = [wd / 2.0, wd / 2.0, wd / 2.0, ht / 2.0] if intrinsics is None else list(intrinsics)
+        self.intrinsics = np.tile(np.array(intr, np.float32) / 4.0, (self.N, 1))
         self.ix = np.repeat(np.arange(self.N), M)
         self.fmap1 = np.zeros((mem, C, self.h, self.w), np.float16)
         self.fmap2 = np.zeros((mem, C, self.h // 4, self.w // 4), np.float16)

@@ -275,6 +275,26 @@ def bench_size():
     print("benchmark-size fixtures written:", out)
 
 
+def _install_patchify_gather():
+    """cuda_corr.patchify_forward (a CUDA kernel, correlation_kernel.cu:16-47) stood in for by a torch gather: integer
+    samples floor(coords) - r .. + r + 1, zero outside the map"""
+    def patchify_forward(net, coords, radius):
+        B, C, H, W = net.shape
+        M, D = coords.shape[1], 2 * radius + 2
+        fx, fy = torch.floor(coords[..., 0]).long(), torch.floor(coords[..., 1]).long()
+        out = torch.zeros((B, M, C, D, D), dtype=net.dtype)
+        bidx = torch.arange(B)[:, None].expand(B, M)
+        for a in range(D):
+            for b in range(D):
+                i, j = fy + (a - radius), fx + (b - radius)
+                ok = (i >= 0) & (i < H) & (j >= 0) & (j < W)
+                v = net[bidx, :, i.clamp(0, H - 1), j.clamp(0, W - 1)]          # [B, M, C]
+                out[:, :, :, a, b] = torch.where(ok[..., None], v, torch.zeros_like(v))
+        return [out]
+
+    sys.modules["cuda_corr"].patchify_forward = patchify_forward
+
+
 def corr_pin():
     """Round 4: the correlation pinned as far as anything of the reference that RUNS here allows.
     corr_forward_kernel + corr_cuda_forward (altcorr/correlation_kernel.cu:82-136,193-233) are CUDA; the one piece of the
@@ -291,22 +311,7 @@ def corr_pin():
     everything after it is the reference executing.  -> corr_pin.npz (inputs + float64 result, both pyramid levels)"""
     _install_shims()
     sys.path.insert(0, REF)
-
-    def patchify_forward(net, coords, radius):
-        B, C, H, W = net.shape
-        M, D = coords.shape[1], 2 * radius + 2
-        fx, fy = torch.floor(coords[..., 0]).long(), torch.floor(coords[..., 1]).long()
-        out = torch.zeros((B, M, C, D, D), dtype=net.dtype)
-        bidx = torch.arange(B)[:, None].expand(B, M)
-        for a in range(D):
-            for b in range(D):
-                i, j = fy + (a - radius), fx + (b - radius)
-                ok = (i >= 0) & (i < H) & (j >= 0) & (j < W)
-                v = net[bidx, :, i.clamp(0, H - 1), j.clamp(0, W - 1)]          # [B, M, C]
-                out[:, :, :, a, b] = torch.where(ok[..., None], v, torch.zeros_like(v))
-        return [out]
-
-    sys.modules["cuda_corr"].patchify_forward = patchify_forward
+    _install_patchify_gather()
     from cdvslam.altcorr import correlation as refcorr
 
     rng = np.random.default_rng(20261004)
@@ -352,10 +357,107 @@ def corr_pin():
           "max |corr0| %.3f, max |corr1| %.3f" % (np.abs(res["corr0"]).max(), np.abs(res["corr1"]).max()))
 
 
+def euroc():
+    """Round 6: the reference's own Python at its EuRoC settings -- 480x752 frames (cdvslam/stream.py:37-38 crops to
+    multiples of 16; level-0 / level-1 maps 120x188 / 30x47) and the calibration of calib/euroc.txt, in which no two of
+    fx, fy, cx, cy are equal (every earlier fixture has fx == fy == cx, under which swapped roles go unnoticed).
+    (i)   projective_ops.py:53-130 on the `tiny` graph at 480x752, per-frame intrinsics with a different factor per
+          component                                                                     -> pops_euroc_f64.npz
+    (ii)  ba.py:86-185, two successive calls at ep = 1.0 on the tiny window graph (two fixed poses), float64, bounds = [-64, -64, 2 cx + 64,
+          2 cy + 64] (== fastba's in-bounds gate, ba_cuda.cu:305-306), with patches moved so that edges reproject into
+          the band 2 cx + 64 < u < W + 64 that only the calibrated gate masks                    -> ba_py_euroc.npz
+    (iii) the corr-pin recipe (below) at 120x188 / 30x47 maps, edges aimed at the odd right / bottom border of level 1;
+          the feature maps are regenerated from the stored seed (tests/golden_util.py) -> corr_pin_euroc.npz"""
+    _install_shims()
+    sys.path.insert(0, REF)
+    _install_patchify_gather()
+    from cdvslam import projective_ops as pops
+    from cdvslam.lietorch import SE3
+    from cdvslam import ba as refba
+    from tests import golden_util
+
+    geo = dict(ht=480, wd=752, intr=synth.EUROC_INTR)
+    # ---- (i) projective ops --------------------------------------------------------------------------
+    st = synth.make_state("tiny", features=False, **geo)
+    tdt = torch.float64
+    poses = torch.from_numpy(st.poses).to(tdt)[None]
+    patches = torch.from_numpy(st.patches).to(tdt)[None]
+    f = torch.arange(st.intrinsics.shape[0], dtype=tdt)[:, None]
+    factor = 1 + f * torch.tensor([0.02, 0.01, 0.005, -0.004], dtype=tdt)       # per frame AND per component
+    intr = (torch.from_numpy(st.intrinsics).to(tdt) * factor)[None]
+    K = intr[0].numpy()
+    assert all(len(set(row)) == 4 for row in K.tolist()) and len(np.unique(K[:, 0])) == len(K)
+    ii, jj, kk = (torch.from_numpy(x) for x in (st.ii, st.jj, st.kk))
+    with torch.no_grad():
+        x1 = pops.transform(SE3(poses), patches, intr, ii, jj, kk)
+        x1j, v, (Ji, Jj, Jz) = pops.transform(SE3(poses), patches, intr, ii, jj, kk, jacobian=True)
+        x1v, val = pops.transform(SE3(poses), patches, intr, ii, jj, kk, valid=True)
+        x1t = pops.transform(SE3(poses), patches, intr, ii, jj, kk, tonly=True)
+        fm, fv = pops.flow_mag(SE3(poses), patches, intr, ii, jj, kk, beta=0.5)
+        m = st.n * st.cfg.M
+        ix = torch.arange(m) // st.cfg.M
+        pc = pops.point_cloud(SE3(poses), patches[:, :m], intr, ix)
+    np.savez_compressed(
+        os.path.join(HERE, "pops_euroc_f64.npz"),
+        poses=poses[0].numpy(), patches=patches[0].numpy(), intrinsics=K, ii=st.ii, jj=st.jj, kk=st.kk,
+        coords=x1[0].numpy(), coords_jac=x1j[0].numpy(), valid=v[0].numpy(), Ji=Ji[0].numpy(), Jj=Jj[0].numpy(),
+        Jz=Jz[0].numpy(), coords_valid=x1v[0].numpy(), validpx=val[0].numpy(), coords_tonly=x1t[0].numpy(),
+        flow_mag=fm[0].numpy(), flow_valid=fv[0].numpy(), point_cloud=pc[0].numpy(), point_cloud_ix=ix.numpy())
+
+    # ---- (ii) ba.py with the calibrated bounds ---------------------------------------------------------
+    st = golden_util.euroc_window_state()
+    band = golden_util.euroc_gate_band(st)
+    poses = torch.from_numpy(st.poses).to(tdt)[None]
+    patches = torch.from_numpy(st.patches).to(tdt)[None]
+    intr = torch.from_numpy(st.intrinsics).to(tdt)[None]
+    ii, jj, kk = (torch.from_numpy(x) for x in (st.ii, st.jj, st.kk))
+    target = torch.from_numpy(st.target).to(tdt)[None]
+    weight = torch.from_numpy(st.weight).to(tdt)[None]
+    fx, fy, cx, cy = (float(a) for a in st.intrinsics[0])
+    bounds = [-64, -64, 2 * cx + 64, 2 * cy + 64]
+    with torch.no_grad():
+        P2, X2 = refba.BA(SE3(poses.clone()), patches.clone(), intr, target, weight, torch.as_tensor([1e-4], dtype=tdt),
+                          ii, jj, kk, bounds, ep=1.0, fixedp=st.t0)
+        P3, X3 = refba.BA(P2, X2, intr, target, weight, torch.as_tensor([1e-4], dtype=tdt), ii, jj, kk, bounds, ep=1.0,
+                          fixedp=st.t0)
+    np.savez_compressed(os.path.join(HERE, "ba_py_euroc.npz"), poses=st.poses, patches=st.patches,
+                        intrinsics=st.intrinsics, target=st.target, weight=st.weight, ii=st.ii, jj=st.jj, kk=st.kk,
+                        bounds=np.array(bounds, np.float64), band=band, t0=np.int64(st.t0), poses1=P2.data[0].numpy(),
+                        patches1=X2[0].numpy(), poses2=P3.data[0].numpy(), patches2=X3[0].numpy())
+
+    # ---- (iii) correlation at the EuRoC map sizes -----------------------------------------------------
+    from cdvslam.altcorr import correlation as refcorr
+    z = golden_util.corr_pin_euroc_inputs()
+    fmap1, fmap2 = z["fmap1"], z["fmap2"]
+    gmap, coords, ii, jj = z["gmap"], z["coords"], z["ii"], z["jj"]
+    E, C = len(ii), gmap.shape[1]
+    res = {}
+    with torch.no_grad():
+        for lvl, (fm, s) in enumerate(((fmap1, 1.0), (fmap2, 4.0))):
+            net = torch.from_numpy(fm).double()
+            g = torch.from_numpy(gmap).double()
+            out = torch.zeros((E, 7, 7, 3, 3), dtype=torch.float64)
+            c = torch.from_numpy(coords) / s
+            for e in range(E):
+                pts = c[e].reshape(2, 9).T[None].contiguous()
+                samp = refcorr.patchify(net[jj[e]][None], pts, 3, mode="bilinear")[0]
+                blended = torch.einsum("cp,pcyx->yxp", g[ii[e]].reshape(C, 9), samp)
+                out[e] = blended.permute(1, 0, 2).reshape(7, 7, 3, 3)
+            res["corr%d" % lvl] = out.numpy()
+    np.savez_compressed(os.path.join(HERE, "corr_pin_euroc.npz"), seed=np.int64(golden_util.CORR_EUROC_SEED),
+                        shape=np.array(fmap1.shape, np.int64), fmap1_sha256=golden_util.sha256_u8(fmap1),
+                        fmap2_sha256=golden_util.sha256_u8(fmap2), gmap=gmap, coords=coords, ii=ii, jj=jj, **res)
+    for f in ("pops_euroc_f64.npz", "ba_py_euroc.npz", "corr_pin_euroc.npz"):
+        print(f, os.path.getsize(os.path.join(HERE, f)), "bytes")
+    print("EuRoC fixtures written: %d gate-band edges, %d corr edges" % (band.sum(), E))
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "bench-size":
         bench_size()
     elif len(sys.argv) > 1 and sys.argv[1] == "corr-pin":
         corr_pin()
+    elif len(sys.argv) > 1 and sys.argv[1] == "euroc":
+        euroc()
     else:
         main()

@@ -82,16 +82,30 @@ def test_out_of_bounds_rule_and_layout():
 
 def test_two_level_stack_on_a_synthetic_state():
     """SLAM.corr on the tiny seeded state: both statements, feature order (x off, y off, i0, j0, level)"""
+    _two_level_stack("tiny", 1)
+
+
+def test_two_level_stack_on_the_euroc_geometry():
+    """the same at `euroc`: 120x188 / 30x47 maps (an odd level-1 width), the 1000-frame patch ring, asymmetric intrinsics
+    (every 37th edge of E = 47,712)"""
+    _two_level_stack("euroc", 37)
+
+
+def _two_level_stack(name, stride):
     from cdv_slam_amd import synth
-    st = synth.make_state("tiny")
-    coords = np.ascontiguousarray(O.transform(st.poses, st.patches, st.intrinsics, st.ii, st.jj, st.kk)
+    st = synth.make_state(name)
+    sel = np.arange(0, st.E, stride)
+    coords = np.ascontiguousarray(O.transform(st.poses, st.patches, st.intrinsics, st.ii[sel], st.jj[sel], st.kk[sel])
                                   .transpose(0, 3, 1, 2))
-    a = O.slam_corr(st.gmap, st.fmap1, st.fmap2, coords, st.ii1, st.jj1, 3, "ref")
-    b = slam_corr_torch(st.gmap, st.fmap1, st.fmap2, coords, st.ii1, st.jj1, 3, "ref").numpy()
-    assert a.shape == b.shape == (st.E, 882)
+    ii1, jj1 = st.ii1[sel], st.jj1[sel]
+    if name == "euroc":    # edges reach past the odd right border of level 1
+        assert st.fmap2.shape[-1] == 47 and (coords[:, 0] / 4 > 46).any()
+    a = O.slam_corr(st.gmap, st.fmap1, st.fmap2, coords, ii1, jj1, 3, "ref")
+    b = slam_corr_torch(st.gmap, st.fmap1, st.fmap2, coords, ii1, jj1, 3, "ref").numpy()
+    assert a.shape == b.shape == (len(sel), 882)
     assert np.array_equal(a.view(np.uint16), b.view(np.uint16))
-    t = O.slam_corr(st.gmap, st.fmap1, st.fmap2, coords, st.ii1, st.jj1, 3, "truth")
-    tb = slam_corr_torch(st.gmap, st.fmap1, st.fmap2, coords, st.ii1, st.jj1, 3, "truth").numpy()
+    t = O.slam_corr(st.gmap, st.fmap1, st.fmap2, coords, ii1, jj1, 3, "truth")
+    tb = slam_corr_torch(st.gmap, st.fmap1, st.fmap2, coords, ii1, jj1, 3, "truth").numpy()
     assert np.abs(t - tb).max() <= 1e-13 * max(1.0, np.abs(t).max())
     # the half path stays inside the envelope the GPU tests allow against the truth (BASELINE.md section 5)
     tol = 2.0 ** -8 * np.abs(t).max() + 2.0 ** -10

@@ -88,9 +88,21 @@ def test_lietorch_classes_golden(golden_dir):
 
 def test_transform_golden(golden_dir):
     """fused cdv_transform vs outputs of the reference's own projective_ops.py"""
+    _transform_vs_pops_fixture(os.path.join(golden_dir, "pops_transform_f32.npz"))
+
+
+def test_transform_golden_euroc(golden_dir):
+    """the same at 480x752 with per-frame EuRoC intrinsics, no two of fx, fy, cx, cy equal (tests/golden/pops_euroc_f64.npz,
+    the reference's projective_ops.py in float64): the roles of fx / fy / cx / cy in tf_pixel and point_cloud are pinned"""
+    g = np.load(os.path.join(golden_dir, "pops_euroc_f64.npz"))
+    assert all(len(set(row)) == 4 for row in g["intrinsics"].tolist())
+    _transform_vs_pops_fixture(os.path.join(golden_dir, "pops_euroc_f64.npz"))
+
+
+def _transform_vs_pops_fixture(path):
     from cdv_slam_amd import projective_ops as pops
     from cdv_slam_amd.lietorch import SE3
-    g = np.load(os.path.join(golden_dir, "pops_transform_f32.npz"))
+    g = {k: (v.astype(np.float32) if v.dtype == np.float64 else v) for k, v in np.load(path).items()}
     poses, patches, intr = T(g["poses"])[None], T(g["patches"])[None], T(g["intrinsics"])[None]
     ii, jj, kk = T(g["ii"]), T(g["jj"]), T(g["kk"])
     x1 = pops.transform(SE3(poses), patches, intr, ii, jj, kk)
@@ -116,7 +128,7 @@ def test_transform_golden(golden_dir):
     assert torch.equal(rp, x1.permute(0, 1, 4, 2, 3).contiguous())
 
 
-@pytest.mark.parametrize("name", ["small", "default"])
+@pytest.mark.parametrize("name", ["small", "default", "euroc"])
 def test_transform_vs_oracle(name):
     st = synth.make_state(name, features=False)
     coords = ops.transform(T(st.poses)[None], T(st.patches)[None], T(st.intrinsics)[None], T(st.ii), T(st.jj),
@@ -242,7 +254,7 @@ def _gpu_coords(st):
                          T(st.kk), layout_e2pp=True)
 
 
-@pytest.mark.parametrize("name", ["tiny", "small", "default", "stress"])
+@pytest.mark.parametrize("name", ["tiny", "small", "default", "stress", "tartan", "euroc"])
 def test_corr_fused_vs_oracle(name):
     """the fused two-level correlation against the float64 oracle -- on the benchmark workload too (default: E = 47,712,
     stress: E = 97,412), both as a direct call (planar tiles) and as the launch bench.py times: UpdatePath.step() with
@@ -253,8 +265,10 @@ def test_corr_fused_vs_oracle(name):
     big = st.E > 20000
     # the channels-last rings hold exactly the reference-layout maps
     assert torch.equal(ops.fmap_interior(up.fmap1).permute(0, 3, 1, 2).cpu(), torch.as_tensor(st.fmap1))
-    # the zero margins stay zero
-    assert float(up.fmap1.float().abs().sum()) == float(ops.fmap_interior(up.fmap1).float().abs().sum())
+    # the zero margins stay zero (every element outside the interior, exactly)
+    margin = up.fmap1.clone()
+    ops.fmap_interior(margin).zero_()
+    assert not margin.any()
     f2 = ops.fmap_interior(up.fmap2).permute(0, 3, 1, 2).float().cpu().numpy()
     assert np.abs(f2 - st.fmap2.astype(np.float32)).max() <= 2.0 ** -11 * np.abs(f2).max() + 1e-7
     coords = _gpu_coords(st)
@@ -293,7 +307,19 @@ def test_corr_vs_reference_run_pin(golden_dir):
     container, contracted with the patch features: tests/golden/make_golden.py corr-pin): cuda_corr.forward per level on
     half and on float32 maps, and the fused two-level launch of the update path on channels-last rings with pixel-major
     and planar tiles.  Half storage: |d| <= 2^-8 max|corr| + 2^-10; float32: 1e-5 relative."""
-    z = np.load(os.path.join(golden_dir, "corr_pin.npz"))
+    _corr_vs_pin(np.load(os.path.join(golden_dir, "corr_pin.npz")), far=(8, 9))
+
+
+def test_corr_vs_reference_run_pin_euroc():
+    """the same against `corr_pin_euroc.npz`: 120x188 level-0 and 30x47 level-1 maps (the odd level-1 width of EuRoC's
+    480x752 frames), edges on the right / bottom border of level 1 (x in {46, 46.5, 47.25, 49.75}) and wide footprints"""
+    from tests import golden_util
+    z = golden_util.load_corr_pin_euroc()
+    assert z["fmap2"].shape[-2:] == (30, 47)
+    _corr_vs_pin(z, far=())
+
+
+def _corr_vs_pin(z, far):
     E = len(z["ii"])
     gmap, f1, f2 = T(z["gmap"]), T(z["fmap1"]), T(z["fmap2"])
     coords, ii, jj = T(z["coords"])[None], T(z["ii"]), T(z["jj"])
@@ -308,7 +334,7 @@ def test_corr_vs_reference_run_pin(golden_dir):
             got32 = ops.corr_forward(gmap[None].float(), fm[None].float(), coords / s, ii, jj, 3)
             assert got32.dtype == torch.float32
             assert np.abs(got32[0].cpu().numpy() - want).max() <= 1e-5 * top
-            assert not got[0, 8].any() and not got[0, 9].any()          # far outside the map
+            assert all(not got[0, e].any() for e in far)                # far outside the map
     finally:
         ops._pairing = saved
     mem, C, H, W = z["fmap1"].shape
@@ -482,8 +508,17 @@ def test_reference_call_sequence_through_the_dropin_names():
     reference's state layouts (cdv_slam_amd.update.DropinPath), on the benchmark workload; equal to UpdatePath.step():
     coordinates, correlation and neighbors bit for bit, the state after the bundle adjustment to the last bits (nothing on
     the path sums in an order that depends on timing)."""
+    _dropin_call_sequence("default")
+
+
+def test_reference_call_sequence_through_the_dropin_names_euroc():
+    """the same at `euroc`: the NHWC shadows of 120x188 / 30x47 maps, the 1000-frame patch ring, the EuRoC intrinsics"""
+    _dropin_call_sequence("euroc")
+
+
+def _dropin_call_sequence(name):
     from cdv_slam_amd.update import DropinPath, UpdatePath
-    st = synth.make_state("default")
+    st = synth.make_state(name)
     dev = torch.device(DEV)
     up = UpdatePath(st, dev)
     want = up.step()
@@ -819,8 +854,17 @@ def test_corr_pixel_major_tiles_bit_identical():
 def test_update_prologue_equals_separate_launches():
     """cdv_update_prologue (ingest + reproject + index histogram in one launch, then the rest of the index build) gives
     bit-identical rings, tiles, coordinates, index and neighbors to the three separate entry points"""
+    _prologue_vs_separate_launches("small")
+
+
+def test_update_prologue_equals_separate_launches_euroc():
+    """the same at `euroc`: the pooled 30x47 level-1 ring (an odd width), the 1000-frame patch ring, EuRoC intrinsics"""
+    _prologue_vs_separate_launches("euroc")
+
+
+def _prologue_vs_separate_launches(name):
     from cdv_slam_amd.update import UpdatePath
-    st = synth.make_state("small")
+    st = synth.make_state(name)
     dev = torch.device(DEV)
     a, b = UpdatePath(st, dev), UpdatePath(st, dev)
     a.fused_prologue, b.fused_prologue = True, False
@@ -881,12 +925,15 @@ def test_corr_edge_cases():
     assert np.abs(got16[0].float().cpu().numpy() - want).max() <= _corr_tol(want)
 
 
-@pytest.mark.parametrize("C", [8, 16, 32])
-def test_corr_two_levels_other_widths(C):
+@pytest.mark.parametrize("C,H,W", [pytest.param(8, 24, 32, id="8"), pytest.param(16, 24, 32, id="16"),
+                                   pytest.param(32, 24, 32, id="32"), pytest.param(24, 44, 60, id="24-44x60"),
+                                   pytest.param(24, 120, 188, id="24-120x188")])
+def test_corr_two_levels_other_widths(C, H, W):
     """the two-level kernel with a run-time feature width (the build for DIMF = 24 is specialised), planar and
-    pixel-major tiles, ring indices that wrap (kk % kmod, jj % jmod, slam.py:319-320) and indices out of range (zeros)"""
-    rng = np.random.default_rng(20 + C)
-    N2, H, W, Ng, M = 5, 24, 32, 12, 300
+    pixel-major tiles, ring indices that wrap (kk % kmod, jj % jmod, slam.py:319-320) and indices out of range (zeros);
+    and maps with odd level-1 sides (11x15, and EuRoC's 30x47) with edges aimed at the right and bottom border of level 1"""
+    rng = np.random.default_rng(20 + C if (H, W) == (24, 32) else 20 + C + H)
+    N2, Ng, M = 5, 12, 300
     f1 = (rng.standard_normal((N2, C, H, W)) / 4).astype(np.float16)
     f2 = f1.reshape(N2, C, H // 4, 4, W // 4, 4).astype(np.float32).mean((3, 5)).astype(np.float16)
     gmap = (rng.standard_normal((Ng, C, 3, 3)) / 4).astype(np.float16)
@@ -896,6 +943,12 @@ def test_corr_two_levels_other_widths(C):
     off = np.arange(3.0) - 1
     coords[:, 0] = cx[:, None, None] + sc[:, None, None] * off[None, None, :]
     coords[:, 1] = cy[:, None, None] + sc[:, None, None] * off[None, :, None]
+    if (H // 4) % 2 or (W // 4) % 2:
+        # level-1 centres on, half a pixel past and beyond the last row / column of an odd-sided level-1 map
+        h1, w1 = H // 4, W // 4
+        edge = np.array([w1 - 1.0, w1 - 0.5, w1 + 0.25, w1 + 2.75])
+        coords[:64, 0] = 4 * np.repeat(edge, 16)[:, None, None] + sc[:64, None, None] * off[None, None, :]
+        coords[64:128, 1] = 4 * np.repeat(edge - w1 + h1, 16)[:, None, None] + sc[64:128, None, None] * off[None, :, None]
     kk = rng.integers(0, 5 * Ng, M).astype(np.int64)     # wraps: kk % Ng
     jj = rng.integers(0, 7 * N2, M).astype(np.int64)     # wraps: jj % N2
     dev = torch.device(DEV)
@@ -988,13 +1041,22 @@ MID_VARIANTS = {"mid15": dict(opt_window=15), "mid19_m5": dict(opt_window=19, M=
 MID_TOL = {"mid32": "pr1"}
 
 
+# the window (N = 10) and mid (N = 21) graphs at EuRoC's 480x752 frames and calibration, in which no two of fx, fy, cx, cy
+# are equal: each keeps the tolerance class of its graph
+EUROC = dict(ht=480, wd=752, intr=synth.EUROC_INTR)
+EUROC_VARIANTS = {"default_euroc": "default", "stress_euroc": "stress"}
+
+
 def _make(name):
     if name in MID_VARIANTS:
         return synth.make_state("small", features=False, **MID_VARIANTS[name]), MID_TOL.get(name, "small")
+    if name in EUROC_VARIANTS:
+        return synth.make_state(EUROC_VARIANTS[name], features=False, **EUROC), EUROC_VARIANTS[name]
     return synth.make_state(name, features=False), name
 
 
-@pytest.mark.parametrize("name", ["small", "init", "pr1", "default", "stress", "mid15", "mid19_m5", "mid11", "mid32"])
+@pytest.mark.parametrize("name", ["small", "init", "pr1", "default", "stress", "mid15", "mid19_m5", "mid11", "mid32",
+                                  "default_euroc", "stress_euroc"])
 def test_ba_intermediates_vs_oracle(name):
     """iteration-0 S, y, C, u, E, dX, dZ against the float64 oracle"""
     st, name = _make(name)
@@ -1012,7 +1074,8 @@ def test_ba_intermediates_vs_oracle(name):
     ba_checks.check_iteration0(name, {k: v.cpu().numpy() for k, v in dbg.items()}, o)
 
 
-@pytest.mark.parametrize("name", ["small", "init", "pr1", "default", "stress", "mid15", "mid19_m5", "mid11", "mid32"])
+@pytest.mark.parametrize("name", ["small", "init", "pr1", "default", "stress", "mid15", "mid19_m5", "mid11", "mid32",
+                                  "default_euroc", "stress_euroc"])
 def test_ba_two_iterations_vs_oracle(name):
     st, name = _make(name)
     poses, patches, _ = _run_ba(st, iterations=2)
@@ -1031,12 +1094,16 @@ def test_ba_two_iterations_vs_oracle(name):
     assert np.all(patches[k0, 2] == patches[k0, 2, :1, :1])
 
 
-@pytest.mark.parametrize("name", ["global", "global_l"])
+@pytest.mark.parametrize("name", ["global", "global_l", "global_euroc"])
 def test_global_ba_vs_oracle(name):
     """more than 32 free poses (slam.py:460-478, eff_impl=True in the reference): panel-sparse Schur products + blocked
     multi-workgroup Cholesky.  Same numbers as the dense path (ba_cuda.cu:567-580 == :583-592), checked against the
-    float64 oracle: intermediates of iteration 0, then the state after two iterations."""
-    st = synth.make_state(name, features=False)
+    float64 oracle: intermediates of iteration 0, then the state after two iterations.  global_euroc: the `global` graph
+    at EuRoC's frames and calibration (tolerance class of `global`)."""
+    if name == "global_euroc":
+        st, name = synth.make_state("global", features=False, **EUROC), "global"
+    else:
+        st = synth.make_state(name, features=False)
     N = st.n - st.t0
     assert N > 32
     _, _, dbg = _run_ba(st, iterations=1, debug=True)
@@ -1284,6 +1351,75 @@ def test_fastba_hip_vs_reference_ba_py_run_on_configs0():
         assert torch.equal(patches[:n * M, 2], patches[:n * M, 2, :1, :1].expand(-1, 3, 3))
 
 
+def test_fastba_hip_vs_reference_ba_py_at_euroc_intrinsics(golden_dir):
+    """the HIP fastba against the reference's own ba.py (float64, two successive calls at ep = 1.0) at the EuRoC calibration
+    with bounds = [-64, -64, 2 cx + 64, 2 cy + 64] -- the gates coincide (tests/test_oracle_golden.py checks it), edges
+    reproject into the band 2 cx + 64 < u < W + 64 -- to the bounds of the well-conditioned class BA_TOL['default'] (two
+    fixed poses anchor scale)"""
+    from cdv_slam_amd import metrics
+    g = np.load(os.path.join(golden_dir, "ba_py_euroc.npz"))
+    n, M, t0 = int(max(g["ii"].max(), g["jj"].max())) + 1, 8, int(g["t0"])
+    tol = ba_checks.BA_TOL["default"]
+    unit = lambda q: q / np.linalg.norm(q, axis=1, keepdims=True)
+    for it, pk, xk in ((1, "poses1", "patches1"), (2, "poses2", "patches2")):
+        poses, patches = T(g["poses"]).clone(), T(g["patches"]).clone()
+        ops.ba_forward(poses, patches, T(g["intrinsics"]), T(g["target"]), T(g["weight"]), torch.tensor([1e-4], device=DEV),
+                       T(g["ii"]), T(g["jj"]), T(g["kk"]), M, t0, n, it, False)
+        torch.cuda.synchronize()
+        p, d, dr = poses.cpu().numpy(), patches[:, 2, 0, 0].cpu().numpy(), g[xk][:, 2, 0, 0]
+        got = dict(t=np.abs(p[:, :3] - g[pk][:, :3]).max(), q=np.abs(unit(p[:, 3:]) - unit(g[pk][:, 3:])).max(),
+                   d=(np.abs(d - dr) / np.maximum(np.abs(dr), 1e-2)).max(), ate=metrics.ate_rmse(g[pk][:n], p[:n]))
+        ba_checks._log("vs_reference_ba_py", "euroc_it%d" % it, got, {k: tol[k] * it for k in got})
+        for k in got:
+            assert got[k] <= tol[k] * it, (it, k, got[k])
+
+
+def test_ba_gate_band_of_the_calibrated_in_bounds_gate():
+    """fastba's in-bounds gate is u < 2 cx + 64, v < 2 cy + 64 (ba_cuda.cu:305-306), not an image-size gate: with EuRoC's
+    cx = 91.8 (W / 2 = 94) edges whose centres reproject into 247.6 < u < 252 carry nonzero weight and must be masked.
+    The HIP window solver equals the float64 oracle on such a graph; the oracle masks those edges (their weights set to
+    zero change nothing, bit for bit), and so does the HIP path."""
+    from tests import golden_util
+    st = golden_util.euroc_window_state()
+    args = lambda w: (st.poses, st.patches, st.intrinsics[0], st.target, w, st.lmbda, st.ii, st.jj, st.kk, st.t0, st.n)
+    # edges in the band at both states the two iterations evaluate the gate at
+    p1, x1, _ = O.fastba(*args(st.weight), 1, np.float64)
+    band = golden_util.euroc_gate_band(st) & golden_util.euroc_gate_band(st, p1)
+    assert band.sum() >= 5 and (st.weight[band] > 0).all()
+    p64, x64, info = O.fastba(*args(st.weight), 2, np.float64)
+    assert info == 0
+    w0 = st.weight.copy()
+    w0[band] = 0
+    q64, y64, _ = O.fastba(*args(w0), 2, np.float64)
+    assert np.array_equal(p64, q64) and np.array_equal(x64, y64)
+    # those edges lie between the calibrated gate and the image-size one
+    u = O.fastba_reproject(st.poses, st.patches, st.intrinsics[0], st.ii, st.jj, st.kk, dtype=np.float64)[:, 0, 1, 1]
+    assert (u[band] > 2 * np.float64(st.intrinsics[0, 2]) + 64).all() and (u[band] < st.cfg.wd // 4 + 64).all()
+    poses, patches, _ = _run_ba(st, iterations=2)
+    tol = ba_checks.BA_TOL["default"]
+    d, d64 = patches[:, 2, 0, 0], x64[:, 2, 0, 0]
+    assert np.abs(poses[:, :3] - p64[:, :3]).max() <= tol["t"] and np.abs(poses[:, 3:] - p64[:, 3:]).max() <= tol["q"]
+    assert (np.abs(d - d64) / np.maximum(np.abs(d64), 1e-2)).max() <= tol["d"]
+    st0 = golden_util.euroc_window_state()
+    st0.weight = w0
+    poses0, patches0, _ = _run_ba(st0, iterations=2)
+    assert np.array_equal(poses, poses0) and np.array_equal(patches, patches0)
+
+
+def test_ba_reads_the_intrinsics_of_row_zero_only():
+    """fastba takes one camera, intrinsics[0] (ba_cuda.cu:255-258): other rows changed -> bit-identical output; row 0
+    changed -> a different one"""
+    from tests import golden_util
+    st = golden_util.euroc_window_state()
+    poses, patches, _ = _run_ba(st, iterations=2)
+    st.intrinsics[1:] *= np.float32([1.1, 0.9, 1.05, 0.95])
+    p1, x1, _ = _run_ba(st, iterations=2)
+    assert np.array_equal(poses, p1) and np.array_equal(patches, x1)
+    st.intrinsics[0] *= np.float32([1.0, 1.0, 1.01, 1.0])
+    p2, x2, _ = _run_ba(st, iterations=2)
+    assert np.abs(p2 - poses).max() > 1e-5
+
+
 def test_patchify_vs_reference_python_layer(golden_dir):
     """altcorr.patchify (one launch: gather + blend) and ops.patchify_multi against the outputs of the reference's own
     cdvslam/altcorr/correlation.py:51-71 (tests/golden/patchify_py.npz): three modes, r = 0 / 1 / 3, f16 and f32 maps,
@@ -1382,21 +1518,30 @@ def test_patchify_frame_in_one_launch():
     """cdv_patchify_multi: the four altcorr.patchify calls of a new frame (net_cdv.py:355-374: imap at the DINO scale with
     the configured sampling mode, gmap, colours at 4 (c + 0.5), patches from the coordinate / inverse-depth grid) against
     the four separate calls on coordinates scaled with torch ops as the reference does -- bit-identical"""
+    _patchify_frame(24, 32, 7, 9)
+
+
+def test_patchify_frame_in_one_launch_euroc():
+    """the same on EuRoC's 120x188 maps with a DINO grid (34x53) that does not divide them"""
+    _patchify_frame(120, 188, 34, 53)
+
+
+def _patchify_frame(h, w, dh, dw):
     from cdv_slam_amd import altcorr
     g = torch.Generator(device="cpu").manual_seed(11)
-    h, w, M = 24, 32, 96
+    M = 96
     fmap = (torch.randn((1, 24, h, w), generator=g) / 4).half().to(DEV)
-    imap = torch.randn((1, 384, 7, 9), generator=g).half().to(DEV)            # DINO features, coarser grid
+    imap = torch.randn((1, 384, dh, dw), generator=g).half().to(DEV)          # DINO features, coarser grid
     image = torch.rand((1, 3, 4 * h, 4 * w), generator=g).to(DEV)
     disps = (torch.rand((h, w), generator=g) * 0.75 + 0.25).to(DEV)
     ys, xs = torch.meshgrid(torch.arange(h, dtype=torch.float32), torch.arange(w, dtype=torch.float32), indexing="ij")
     grid = torch.stack([xs.to(DEV), ys.to(DEV), disps])[None]               # coords_grid_with_index: (x, y, disparity)
     coords = torch.stack([torch.rand(M, generator=g) * (w + 4) - 2, torch.rand(M, generator=g) * (h + 4) - 2], -1)[None].to(DEV)
-    s_f2i = torch.tensor([9.0 / w, 7.0 / h], device=DEV)                      # (x, y) scale feature grid -> DINO grid
+    s_f2i = torch.tensor([float(dw) / w, float(dh) / h], device=DEV)           # (x, y) scale feature grid -> DINO grid
     for imode in ("bilinear", "upperleft"):
         want = [altcorr.patchify(imap, s_f2i * coords, 0, mode=imode), altcorr.patchify(fmap, coords, 1),
                 altcorr.patchify(image, 4 * (coords + 0.5), 0), altcorr.patchify(grid, coords, 1)]
-        got = ops.patchify_multi([dict(net=imap, radius=0, mode=imode, scale=(9.0 / w, 7.0 / h)),
+        got = ops.patchify_multi([dict(net=imap, radius=0, mode=imode, scale=(float(dw) / w, float(dh) / h)),
                                   dict(net=fmap, radius=1), dict(net=image, radius=0, scale=4.0, offset=0.5),
                                   dict(net=grid, radius=1)], coords)
         for a, b in zip(got, want):

@@ -271,3 +271,138 @@ def test_block_sparse_E_of_the_reference_equals_its_dense_branch(window):
     be.ij_xself = be.ij_xself[::-1].copy()
     be.fill(st.kk, w, Jz, Ji, Jj)
     assert np.abs(be.computeEQEt(N, Q) - (o["E"] * Q) @ o["E"].T).max() > 1e-2 * np.abs((o["E"] * Q) @ o["E"].T).max()
+
+
+# ---------------------------------------------------------------------------------------------------
+# round 6: the reference's camera geometries and intrinsics (tests/golden/make_golden.py euroc)
+# ---------------------------------------------------------------------------------------------------
+
+def test_configs_at_the_reference_geometries():
+    """`tartan` (480x640, TartanAir's symmetric calibration) and `euroc` (480x752, calib/euroc.txt) keep the benchmark graph
+    (E = 47,712) while the maps, the intrinsics and the patch ring change; the default configs keep their formula"""
+    from cdv_slam_amd import synth
+    for name, hw in (("tartan", (120, 160)), ("euroc", (120, 188))):
+        st = synth.make_state(name, features=False)
+        assert st.E == 47712 == synth.make_state("default", features=False).E
+        assert (st.cfg.ht // st.cfg.res, st.cfg.wd // st.cfg.res) == hw
+        assert np.array_equal(st.intrinsics, np.tile(np.float32(np.array(st.cfg.intr) / 4), (st.cfg.buffer_size, 1)))
+    st = synth.make_state("euroc")
+    assert st.fmap1.shape[-2:] == (120, 188) and st.fmap2.shape[-2:] == (30, 47)
+    assert st.cfg.pmem == 1000 and st.cfg.buffer_size == 4096 and st.gmap.shape[0] == 96000
+    fx, fy, cx, cy = st.intrinsics[0]
+    assert len({fx, fy, cx, cy}) == 4 and 2 * cx + 64 < st.cfg.wd // 4 + 64 - 4
+    d = synth.make_state("default", features=False)
+    assert np.array_equal(d.intrinsics[0], np.float32([64, 64, 64, 48]))
+
+
+def test_pops_euroc_golden(golden_dir):
+    """projective_ops.py:53-130 at 480x752 with per-frame EuRoC intrinsics in which no two of fx, fy, cx, cy are equal:
+    coords, Jacobians, validity, tonly, flow_mag and point_cloud as the reference's own file computed them in float64
+    (tolerances of test_pops_transform_golden); exchanging two intrinsics is far off"""
+    g = np.load(os.path.join(golden_dir, "pops_euroc_f64.npz"))
+    K = g["intrinsics"]
+    assert all(len(set(row)) == 4 for row in K.tolist())
+    dt, tol = np.float64, 1e-11
+    args = (g["poses"], g["patches"], K, g["ii"], g["jj"], g["kk"])
+    coords = O.transform(*args, dtype=dt)
+    assert np.allclose(coords, g["coords"], rtol=0, atol=tol * 100)
+    c2, v, (Ji, Jj, Jz) = O.transform(*args, jacobian=True, dtype=dt)
+    assert np.array_equal(v, g["valid"])
+    for a, b in ((Ji, g["Ji"]), (Jj, g["Jj"]), (Jz, g["Jz"])):
+        assert np.allclose(a, b, rtol=tol * 10, atol=tol * np.abs(b).max())
+    c3, vpx = O.transform(*args, valid=True, dtype=dt)
+    assert np.array_equal(vpx, g["validpx"])
+    assert np.allclose(O.transform(*args, tonly=True, dtype=dt), g["coords_tonly"], rtol=0, atol=tol * 100)
+    ii, jj, kk = g["ii"], g["jj"], g["kk"]
+    c0 = O.transform(g["poses"], g["patches"], K, ii, ii, kk, dtype=dt)
+    c1 = O.transform(g["poses"], g["patches"], K, ii, jj, kk, tonly=True, dtype=dt)
+    flow = 0.5 * np.linalg.norm(coords - c0, axis=-1) + 0.5 * np.linalg.norm(c1 - c0, axis=-1)
+    assert np.allclose(flow, g["flow_mag"], atol=1e-9)
+    assert np.array_equal(vpx > 0.5, g["flow_valid"])
+    ix = g["point_cloud_ix"]
+    Pinv = O.lie(O.SE3, "inv", g["poses"][ix], dtype=dt)
+    patches, Kx = g["patches"][:len(ix)], K[ix]
+    X0 = np.stack([(patches[:, 0] - Kx[:, 2, None, None]) / Kx[:, 0, None, None],
+                   (patches[:, 1] - Kx[:, 3, None, None]) / Kx[:, 1, None, None],
+                   np.ones_like(patches[:, 2]), patches[:, 2]], -1)
+    pc = O.lie(O.SE3, "act4", np.repeat(Pinv, 9, axis=0), X0.reshape(-1, 4), dtype=dt).reshape(X0.shape)
+    assert np.allclose(pc, g["point_cloud"], atol=1e-10)
+    # the fixture pins the roles: fx <-> cx or fx <-> fy exchanged moves the points by pixels
+    for a, b in ((0, 2), (0, 1), (2, 3)):
+        Ks = K.copy()
+        Ks[:, [a, b]] = Ks[:, [b, a]]
+        assert np.abs(O.transform(g["poses"], g["patches"], Ks, ii, jj, kk, dtype=dt) - g["coords"]).max() > 0.1, (a, b)
+
+
+def test_fastba_matches_reference_ba_py_at_euroc_intrinsics(golden_dir):
+    """fastba (ba_cuda.cu) == the reference's own ba.py, two successive calls at ep = 1.0 in float64, at the EuRoC
+    calibration with bounds = [-64, -64, 2 cx + 64, 2 cy + 64]: ba.py's bounds gate then coincides with fastba's in-bounds
+    gate (ba_cuda.cu:305-306).  Edges reproject into 2 cx + 64 < u < W + 64, where that gate and an image-size one differ;
+    an image-size gate (cx read as W / 2) gives a different answer."""
+    from tests import golden_util
+    g = np.load(os.path.join(golden_dir, "ba_py_euroc.npz"))
+    st = golden_util.euroc_window_state()
+    for k in ("poses", "patches", "intrinsics", "target", "weight", "ii", "jj", "kk"):
+        assert np.array_equal(getattr(st, k), g[k]), k
+    K = g["intrinsics"][0]
+    assert len(set(K.tolist())) == 4 and np.array_equal(g["intrinsics"], np.tile(K, (len(g["intrinsics"]), 1)))
+    assert np.array_equal(g["bounds"], [-64, -64, 2 * np.float64(K[2]) + 64, 2 * np.float64(K[3]) + 64])
+    n, t0 = int(max(g["ii"].max(), g["jj"].max())) + 1, int(g["t0"])
+    assert t0 == st.t0 == 2
+    # the band is populated at every state the two iterations evaluate the gate at, with no centre within 0.25 px of it
+    for P, X in ((g["poses"], g["patches"]), (g["poses1"], g["patches1"])):
+        u = O.fastba_reproject(P, X, K, g["ii"], g["jj"], g["kk"], dtype=np.float64)[:, :, 1, 1]
+        assert ((u[:, 0] > g["bounds"][2]) & (u[:, 0] < 188 + 64)).sum() >= 5
+        assert np.abs(u[:, 0] - g["bounds"][2]).min() > 0.25
+        assert np.linalg.norm(g["target"] - u, axis=-1).max() < 128 and (u[:, 1] < g["bounds"][3] - 1).all()
+    assert golden_util.euroc_gate_band(st).sum() == g["band"].sum() >= 5
+    args = (g["target"], g["weight"], 1e-4, g["ii"], g["jj"], g["kk"], t0, n)
+    for it, pk, xk in ((1, "poses1", "patches1"), (2, "poses2", "patches2")):
+        p, x, info = O.fastba(g["poses"], g["patches"], K, *args, iterations=it, dtype=np.float64)
+        assert info == 0
+        # ba.py's lietorch retraction renormalises the quaternions, fastba carries the float32 input's |q| - 1 (~1e-8)
+        unit = lambda q: q / np.linalg.norm(q, axis=1, keepdims=True)
+        assert np.abs(p[:, :3] - g[pk][:, :3]).max() < 1e-9, it
+        assert np.abs(unit(p[:, 3:]) - unit(g[pk][:, 3:])).max() < 1e-9, it
+        d, dr = x[:, 2, 0, 0], g[xk][:, 2, 0, 0]
+        ok = (dr > 1.001e-3) & (dr < 9.99)                  # ba.py's depth clamps (ba.py:179) do not fire
+        assert ok.sum() >= 0.9 * len(ok)
+        assert np.abs(d[ok] - dr[ok]).max() < 1e-8, it
+    # oracle/ba_py.py, the restatement of ba.py, with the same bounds
+    P1, X1, info = ba_py.BA(g["poses"], g["patches"], g["intrinsics"], g["target"], g["weight"], 1e-4, g["ii"], g["jj"],
+                            g["kk"], g["bounds"], ep=1.0, fixedp=t0, dtype=np.float64)
+    assert info == 0 and np.abs(P1 - g["poses1"]).max() < 1e-9
+    # negative control: the image-size gate (what the calibrated gate looks like when cx == W / 2) keeps the band's edges
+    wide = np.array([-64, -64, 188 + 64, 120 + 64], np.float64)
+    Pw, _, _ = ba_py.BA(g["poses"], g["patches"], g["intrinsics"], g["target"], g["weight"], 1e-4, g["ii"], g["jj"], g["kk"],
+                        wide, ep=1.0, fixedp=t0, dtype=np.float64)
+    assert np.abs(Pw - g["poses1"]).max() > 1e-6
+
+
+def test_corr_oracle_vs_reference_run_pin_euroc(golden_dir):
+    """corr-pin at the EuRoC map sizes (120x188 level 0, 30x47 level 1 from torch's avg_pool2d as slam.py:682): the oracle
+    and the independent torch statement (tests/corr_torch_ref.py) against the reference's own patchify blend, with edges on
+    the odd right / bottom border of level 1 and wide footprints"""
+    from tests import golden_util
+    from tests.corr_torch_ref import slam_corr_torch
+    z = golden_util.load_corr_pin_euroc()
+    assert z["fmap1"].shape[-2:] == (120, 188) and z["fmap2"].shape[-2:] == (30, 47)
+    g32 = z["gmap"].astype(np.float32)
+    for lvl, (fm, s) in enumerate(((z["fmap1"], 1.0), (z["fmap2"], 4.0))):
+        c = (z["coords"] / np.float32(s)).astype(np.float32)
+        want = z["corr%d" % lvl]
+        top = np.abs(want).max()
+        truth = O.corr(g32, fm.astype(np.float32), c, z["ii"], z["jj"], 3, "truth")
+        assert np.abs(truth - want).max() <= 2e-7 * top
+        assert np.abs(truth.transpose(0, 2, 1, 3, 4) - want).max() > 0.1 * top
+        f32 = O.corr(g32, fm.astype(np.float32), c, z["ii"], z["jj"], 3, "f32")
+        assert np.abs(f32 - want).max() <= 1e-5 * top
+        half = O.corr(z["gmap"], fm, c, z["ii"], z["jj"], 3, "ref").astype(np.float64)
+        assert np.abs(half - want).max() <= 2.0 ** -8 * top + 2.0 ** -10
+    # the level-1 border edges see the last column (x = 46) and nothing beyond it
+    assert np.abs(z["corr1"][:16]).max() > 0.05 * np.abs(z["corr1"]).max()
+    want = np.stack([z["corr0"], z["corr1"]], -1).reshape(len(z["ii"]), -1)      # slam.py:323
+    args = (z["gmap"].astype(np.float32), z["fmap1"].astype(np.float32), z["fmap2"].astype(np.float32), z["coords"],
+            z["ii"], z["jj"], 3, "truth")
+    assert np.abs(O.slam_corr(*args) - want).max() <= 2e-7 * np.abs(want).max()
+    assert np.abs(slam_corr_torch(*args).numpy() - want).max() <= 2e-7 * np.abs(want).max()

@@ -67,17 +67,27 @@ def test_closed_loop_stream_with_the_reference_keyframe_test():
 
 def _pair_dev(gain, **kw):
     from cdv_slam_amd.stream import DeviceStreamRunner
-    return DeviceStreamRunner(torch.device(DEV), gain=gain, **CFG, **kw), StreamOracle(gain=gain, **CFG, **kw)
+    kw = {**CFG, **kw}
+    return DeviceStreamRunner(torch.device(DEV), gain=gain, **kw), StreamOracle(gain=gain, **kw)
 
 
-@pytest.mark.parametrize("gain", [0.01, 0.25])
-def test_device_stream_with_dropped_keyframes(gain):
-    run, so = _pair_dev(gain)
+# the EuRoC camera: 480x752 frames (maps 120x188 / 30x47) and calib/euroc.txt, in which no two of fx, fy, cx, cy are equal
+EUROC = dict(ht=480, wd=752, intrinsics=(458.654, 457.296, 367.215, 248.375))
+
+
+@pytest.mark.parametrize("gain,geo", [pytest.param(0.01, {}, id="0.01"), pytest.param(0.25, {}, id="0.25"),
+                                      pytest.param(0.01, EUROC, id="euroc-0.01")])
+def test_device_stream_with_dropped_keyframes(gain, geo):
+    run, so = _pair_dev(gain, **geo)
+    if geo:
+        from cdv_slam_amd import ops
+        assert tuple(ops.fmap_interior(run.fmap2).shape[1:3]) == (30, 47)
+        assert np.array_equal(run.intrinsics[0].cpu().numpy(), so.intrinsics[0]) and len(set(so.intrinsics[0].tolist())) == 4
     res = closed_loop(run, so, frames=132, drop="pattern")
     assert res["edges_identical"], res.get("first_mismatch")
     assert res["frames"] == 132 and res["dropped"] >= 35 and res["keyframes"] >= 60
     ate = metrics.ate_rmse(res["poses_oracle"], res["poses_gpu"])
-    _log("device_stream_pattern", "gain%g" % gain, {"ate": ate, "frames": res["frames"], "keyframes": res["keyframes"],
+    _log("device_stream_pattern", ("euroc_" if geo else "") + "gain%g" % gain, {"ate": ate, "frames": res["frames"], "keyframes": res["keyframes"],
                                                    "dropped": res["dropped"]}, {"ate": ATE_TOL})
     assert ate <= ATE_TOL
     rel = np.abs(res["patches_gpu"] - res["patches_oracle"]) / np.abs(res["patches_oracle"])
