@@ -36,6 +36,10 @@ SIGNATURES = {
     "cdv_gmap_to_pixel_major": (_i32, [_vp, _vp, _i64, _i32, _i64, _i64, _vp]),
     "cdv_frame_ingest": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i64, _i64, _i64, _vp]),
     "cdv_patchify_fwd": (_i32, [_vp, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "cdv_corr_bwd_workspace_bytes": (_sz, [_i64, _i64, _i64, _i32, _i32, _i32, _i32]),
+    "cdv_corr_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "cdv_patchify_bwd_workspace_bytes": (_sz, [_i32, _i64, _i32, _i32, _i32]),
+    "cdv_patchify_bwd": (_i32, [_vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
     "cdv_loop_flow": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp]),
     "cdv_patchify_multi": (_i32, [_vp, _i32, _vp, _i64, _vp]),
     "cdv_patchify_blend": (_i32, [_vp, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),

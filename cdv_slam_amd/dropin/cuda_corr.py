@@ -8,7 +8,8 @@ def forward(fmap1, fmap2, coords, ii, jj, radius):
 
 
 def backward(fmap1, fmap2, coords, ii, jj, corr_grad, radius):
-    raise NotImplementedError("cuda_corr.backward is the training path (out of scope: inference runs under no_grad)")
+    """corr_backward (correlation.cpp:37-45) -> [fmap1_grad, fmap2_grad]; float32 maps (TypeError otherwise)"""
+    return list(ops.corr_backward(fmap1, fmap2, coords, ii, jj, corr_grad, int(radius)))
 
 
 def patchify_forward(net, coords, radius):
@@ -17,4 +18,5 @@ def patchify_forward(net, coords, radius):
 
 
 def patchify_backward(net, coords, gradient, radius):
-    raise NotImplementedError("cuda_corr.patchify_backward is the training path (out of scope)")
+    """patchify_backward (correlation.cpp:52-55) -> [net_grad]"""
+    return [ops.patchify_backward(net, coords, gradient, int(radius))]

@@ -1041,6 +1041,80 @@ def patchify_blend(net, coords, radius, mode):
     return out
 
 
+def corr_forward_plain(fmap1, fmap2, coords, ii, jj, radius):
+    """corr_forward on the generic planar kernel alone (cdv_corr_fwd): never a fused or paired-level result.  The
+    forward of altcorr.corr under autograd; float32 maps give the values of the no-grad float32 call bit for bit."""
+    lib = _lib.load()
+    _need_cuda(fmap1, fmap2, coords, ii, jj)
+    if fmap1.dtype != fmap2.dtype or fmap1.dtype not in (torch.float16, torch.float32):
+        raise TypeError("corr: feature maps must both be float16 or float32")
+    if coords.dtype != torch.float32:
+        raise TypeError("corr: coords must be float32 (correlation_kernel.cu:86)")
+    B, N1, C, P = fmap1.shape[0], fmap1.shape[1], fmap1.shape[2], fmap1.shape[3]
+    N2, H2, W2 = fmap2.shape[1], fmap2.shape[3], fmap2.shape[4]
+    M, D1 = coords.shape[1], 2 * radius + 1
+    fmap1, fmap2, coords = fmap1.contiguous(), fmap2.contiguous(), coords.contiguous()
+    ii, jj = ii.contiguous(), jj.contiguous()
+    out = torch.empty((B, M, D1, D1, P, P), dtype=fmap1.dtype, device=fmap1.device)
+    for b in range(B):
+        rc = lib.cdv_corr_fwd(_p(fmap1[b]), _p(fmap2[b]), _p(coords[b]), _p(ii), _p(jj), _p(out[b]), M, N1, N2, C, P,
+                              H2, W2, radius, _DT[fmap1.dtype], _stream())
+        _lib.check(rc, "cdv_corr_fwd")
+    return out
+
+
+def corr_backward(fmap1, fmap2, coords, ii, jj, grad, radius, need=(True, True)):
+    """cuda_corr.backward (correlation_kernel.cu:236-285): fmap1 [B,N1,C,P,P], fmap2 [B,N2,C,H2,W2], coords
+    [B,M,2,P,P] f32, grad [B,M,2r+1 (x),2r+1 (y),P,P] of any strides -> (fmap1_grad | None, fmap2_grad | None) in
+    the maps' dtype, shape and device; `need` says which (ctx.needs_input_grad).  float32 maps only: the reference's
+    backward reads the window gradient through a float accessor.  Deterministic (cdv_corr_bwd: no float atomics)."""
+    if fmap1.dtype != torch.float32 or fmap2.dtype != torch.float32:
+        raise TypeError("corr_backward: feature maps must be float32 (the reference's backward, correlation_kernel.cu:"
+                        "139-190, reads the gradient as float; got %s / %s)" % (fmap1.dtype, fmap2.dtype))
+    _need_cuda(fmap1, fmap2, coords, ii, jj, grad)
+    lib = _lib.load()
+    B, N1, C, P = fmap1.shape[0], fmap1.shape[1], fmap1.shape[2], fmap1.shape[3]
+    N2, H2, W2 = fmap2.shape[1], fmap2.shape[3], fmap2.shape[4]
+    M = coords.shape[1]
+    need1, need2 = bool(need[0]), bool(need[1])
+    f1, f2 = fmap1.contiguous(), fmap2.contiguous()
+    coords = coords.contiguous().float()
+    ii, jj = ii.contiguous().long(), jj.contiguous().long()
+    grad = grad.contiguous().float()
+    g1 = torch.empty(fmap1.shape, dtype=fmap1.dtype, device=fmap1.device) if need1 else None
+    g2 = torch.empty(fmap2.shape, dtype=fmap2.dtype, device=fmap2.device) if need2 else None
+    if not (need1 or need2):
+        return None, None
+    ws = torch.empty(max(int(lib.cdv_corr_bwd_workspace_bytes(M, N1, N2, P, H2, W2, radius)), 1), dtype=torch.uint8,
+                     device=fmap1.device)
+    for b in range(B):
+        rc = lib.cdv_corr_bwd(_p(f1[b]), _p(f2[b]), _p(coords[b]), _p(ii), _p(jj), _p(grad[b]),
+                              _p(g1[b]) if need1 else None, _p(g2[b]) if need2 else None, _p(ws), M, N1, N2, C, P, H2,
+                              W2, radius, _stream())
+        _lib.check(rc, "cdv_corr_bwd")
+    return g1, g2
+
+
+def patchify_backward(net, coords, patch_grad, radius):
+    """cuda_corr.patchify_backward (correlation_kernel.cu:310-333): net [B,C,H,W] f16/f32, coords [B,M,2],
+    patch_grad [B,M,C,D,D] -> net_grad shaped like net, in its dtype.  Sums in float32 and rounds once (the reference
+    accumulates float16 in float16); deterministic (cdv_patchify_bwd: no float atomics)."""
+    if net.dtype not in (torch.float16, torch.float32):
+        raise TypeError("patchify_backward: net must be float16 or float32")
+    _need_cuda(net, coords, patch_grad)
+    lib = _lib.load()
+    B, C, H, W = net.shape
+    M = coords.shape[1]
+    coords = coords.contiguous().float()
+    pg = patch_grad.contiguous().to(net.dtype)
+    out = torch.empty(net.shape, dtype=net.dtype, device=net.device)
+    ws = torch.empty(max(int(lib.cdv_patchify_bwd_workspace_bytes(B, M, H, W, radius)), 1), dtype=torch.uint8,
+                     device=net.device)
+    rc = lib.cdv_patchify_bwd(_p(pg), _p(coords), _p(out), _p(ws), B, M, C, H, W, radius, _DT[net.dtype], _stream())
+    _lib.check(rc, "cdv_patchify_bwd")
+    return out
+
+
 def patchify_multi(jobs, coords):
     """The altcorr.patchify calls of one new frame (net_cdv.py:355-374) in ONE launch (cdv_patchify_multi).
     jobs: list of dicts {net [C,H,W] or [1,C,H,W] f16/f32, radius, mode 'bilinear'|'upperleft', scale (sx, sy) or

@@ -217,6 +217,35 @@ int cdv_patchify_fwd(const void* net, const float* coords, void* patches, int B,
                      int radius, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * altcorr backward  (replaces cuda_corr.backward / patchify_backward: training)
+ * Destination gathers: every output element is summed by one lane in a fixed order and stored once, so results are
+ * bitwise reproducible, need no zero-filled output and use no float atomics.  Six kernel launches per call on
+ * `stream`, no host synchronisation (capturable into a graph).  `workspace` holds at least the bytes the matching
+ * *_workspace_bytes query returns (shapes only); its contents need no initialisation.
+ * ---------------------------------------------------------------------------------------------- */
+
+/*
+ * cuda_corr.backward(fmap1, fmap2, coords, ii, jj, grad, radius) -- correlation_kernel.cu:139-190, :236-285, one
+ * batch element.  Layouts as cdv_corr_fwd, float32 only:
+ *   grad        [M][D-1 (x)][D-1 (y)][P][P] f32, contiguous (the layout cdv_corr_fwd writes)
+ *   fmap1_grad  [N1][C][P][P] f32, or NULL when not needed
+ *   fmap2_grad  [N2][C][H2][W2] f32, or NULL when not needed
+ * Edges whose us / vs fall outside [0, N1) / [0, N2) contribute nothing (the forward gives them zero), as do windows
+ * wholly off the map; coordinates are clamped like the forward's.  Any C, P, radius with P^2 (2r+2)^2 floats <= 60 KiB.
+ */
+size_t cdv_corr_bwd_workspace_bytes(int64_t M, int64_t N1, int64_t N2, int P, int H2, int W2, int radius);
+int cdv_corr_bwd(const float* fmap1, const float* fmap2, const float* coords, const int64_t* us, const int64_t* vs,
+                 const float* grad, float* fmap1_grad, float* fmap2_grad, void* workspace, int64_t M, int64_t N1,
+                 int64_t N2, int C, int P, int H2, int W2, int radius, void* stream);
+
+/* cuda_corr.patchify_backward(net, coords, gradient, radius) -- correlation_kernel.cu:49-80, :310-333: the adjoint of
+ * cdv_patchify_fwd.  patch_grad [B][M][C][D][D], coords [B][M][2] f32 -> net_grad [B][C][H][W] (every element
+ * written).  dtype CDV_F16 or CDV_F32 for patch_grad and net_grad alike; sums in f32, one rounding at the store. */
+size_t cdv_patchify_bwd_workspace_bytes(int B, int64_t M, int H, int W, int radius);
+int cdv_patchify_bwd(const void* patch_grad, const float* coords, void* net_grad, void* workspace, int B, int64_t M,
+                     int C, int H, int W, int radius, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * projective ops  (replaces the ~15 launches of pops.transform, projective_ops.py:53-113)
  * ---------------------------------------------------------------------------------------------- */
 
