@@ -100,7 +100,9 @@ class StreamOracle:
         p, x, info = O.fastba(self.poses, self.patches, self.intrinsics[0], e.target, e.weight, 1e-4, e.ii, e.jj, e.kk, t0, n,
                               2, self.dtype)
         self.poses, self.patches = p.astype(np.float32), x.astype(np.float32)
-        self.last = {"coords": coords, "corr": corr, "t0": t0, "info": info}
+        # (the lists as this update saw them: keyframe() below renumbers and prunes e.ii / e.jj / e.kk)
+        self.last = {"coords": coords, "corr": corr, "t0": t0, "info": info, "ii": e.ii.copy(), "jj": e.jj.copy(),
+                     "kk": e.kk.copy()}
         # slam.py:524-526: the world points of every patch so far
         m = n * M
         Pinv = O.lie(O.SE3, "inv", self.poses[self.ix[:m]], dtype=np.float32)
@@ -161,13 +163,15 @@ class StreamOracle:
         return self.n, len(e.ii)
 
 
-def closed_loop(run, so, frames, seed=1234, drop="pattern", check_edges=True, progress=None):
+def closed_loop(run, so, frames, seed=1234, drop="pattern", check_edges=True, progress=None, audit=None):
     """Drive the GPU stream runner `run` (cdv_slam_amd.stream.StreamRunner) and the oracle runner `so` side by side over
     `frames` frames from the same stubbed network outputs.  drop: "pattern" = frame n - 4 leaves on every third frame
     (the caller's decision, identical on both sides); "flow" = each side applies the reference's own test to ITS state
     (mean flow under KEYFRAME_THRESH, slam.py:409-413) and the decisions are compared.  Returns a dict: frames run,
     keyframes kept, edges, whether every frame's edge lists were bit-identical, the decisions that differed, the largest
-    |motion| difference, and the final trajectories (poses of the keyframes) of both sides."""
+    |motion| difference, and the final trajectories (poses of the keyframes) of both sides.  audit: None, or a callable
+    run after every frame (once the edge lists have been compared) as audit(f, run, so, dropped), dropped = whether the
+    frame removed keyframe n - 4."""
     import torch
     rng = np.random.default_rng(seed)
     M, C, h, w = so.M, so.C, so.h, so.w
@@ -184,7 +188,8 @@ def closed_loop(run, so, frames, seed=1234, drop="pattern", check_edges=True, pr
         n_o, E_o = so.frame(pool[f % 4], cx, cy, d, drop=want)
         run.frame(drop=want, inputs=(pool_dev[f % 4], T(cx), T(cy), T(d)))
         n_g, E_g = run.counts()
-        res["dropped"] += int(n_o == n0)
+        dropped = n_o == n0
+        res["dropped"] += int(dropped)
         if drop == "flow" and so.last_motion is not None:
             res["motion_maxdiff"] = max(res["motion_maxdiff"], abs(so.last_motion - run.last_motion))
             if (so.last_motion < so.kthresh) != (run.last_motion < run.kthresh):
@@ -198,6 +203,8 @@ def closed_loop(run, so, frames, seed=1234, drop="pattern", check_edges=True, pr
             res["edges_identical"] = False
             res["first_mismatch"] = f
             break
+        if audit is not None:
+            audit(f, run, so, dropped)
         res["frames"] = f + 1
         if progress is not None and f % 20 == 19:
             progress("closed loop: frame %d, %d keyframes, %d edges" % (f + 1, n_o, E_o))

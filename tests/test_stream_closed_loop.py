@@ -13,6 +13,7 @@ import torch
 from cdv_slam_amd import metrics
 from oracle.stream_py import StreamOracle, closed_loop
 from tests.ba_checks import _log
+from tests.stream_audit import StreamAudit
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -83,9 +84,14 @@ def test_device_stream_with_dropped_keyframes(gain, geo):
         from cdv_slam_amd import ops
         assert tuple(ops.fmap_interior(run.fmap2).shape[1:3]) == (30, 47)
         assert np.array_equal(run.intrinsics[0].cpu().numpy(), so.intrinsics[0]) and len(set(so.intrinsics[0].tolist())) == 4
-    res = closed_loop(run, so, frames=132, drop="pattern")
+    # every update audited (tests/stream_audit.py); at gain 0.25 the correlation of every third kept frame
+    aud = StreamAudit(("euroc_" if geo else "") + "gain%g" % gain, corr_every=1 if gain == 0.01 else 3)
+    aud.arm(run)
+    res = closed_loop(run, so, frames=132, drop="pattern", audit=aud)
     assert res["edges_identical"], res.get("first_mismatch")
     assert res["frames"] == 132 and res["dropped"] >= 35 and res["keyframes"] >= 60
+    aud.log("device_stream_pattern_audit")
+    assert aud.counts["frames"] == 132 and aud.counts["corr"] >= (75 if gain == 0.01 else 25)
     ate = metrics.ate_rmse(res["poses_oracle"], res["poses_gpu"])
     _log("device_stream_pattern", ("euroc_" if geo else "") + "gain%g" % gain, {"ate": ate, "frames": res["frames"], "keyframes": res["keyframes"],
                                                    "dropped": res["dropped"]}, {"ate": ATE_TOL})
@@ -108,7 +114,11 @@ def test_device_stream_with_the_reference_keyframe_test():
     """the decision never leaves the device (slam.py:409-413 reads it back twice per frame): flow statistic -> compare ->
     conditional removal, index shift and buffer shift, all in the launches of cdv_stream_keyframe"""
     run, so = _pair_dev(0.01, keyframe_thresh=2.5)
-    res = closed_loop(run, so, frames=126, drop="flow")
+    aud = StreamAudit("flow_gain0.01", corr_every=3)
+    aud.arm(run)
+    res = closed_loop(run, so, frames=126, drop="flow", audit=aud)
+    aud.log("device_stream_flow_audit")
+    assert aud.counts["frames"] == res["frames"] and aud.counts["corr"] >= 5
     assert not res["decisions_differ"], res["decisions_differ"]
     assert res["motion_maxdiff"] <= 1e-3
     assert res["edges_identical"], res.get("first_mismatch")
@@ -127,7 +137,11 @@ def test_device_stream_with_the_wide_optimisation_window(drop):
     every frame, the same keyframe decisions, ATE within BASELINE.json's tolerance, no failure event."""
     kw = dict(opt_window=22, keyframe_thresh=2.5) if drop == "flow" else dict(opt_window=22)
     run, so = _pair_dev(0.01, **kw)
-    res = closed_loop(run, so, frames=110, drop=drop)
+    aud = StreamAudit("window22_" + drop, corr_every=1 if drop == "pattern" else 3)
+    aud.arm(run)
+    res = closed_loop(run, so, frames=110, drop=drop, audit=aud)
+    aud.log("device_stream_window22_audit")
+    assert aud.counts["frames"] == res["frames"] and aud.counts["corr"] >= (40 if drop == "pattern" else 5)
     if drop == "flow":
         assert not res["decisions_differ"], res["decisions_differ"]
         assert res["motion_maxdiff"] <= 1e-3
@@ -206,6 +220,20 @@ def test_device_stream_two_frames_as_a_hipgraph():
     assert torch.equal(a.poses[:n], b.poses[:n]) and torch.equal(a.patches[:n * a.M], b.patches[:n * a.M])
     assert a.E_inac == b.E_inac
     assert a.events.counts() == [0, 0, 0, 0] and b.events.counts() == [0, 0, 0, 0]
+    _audit_one_more_frame(a, "hipgraph_pair")
+
+
+def _audit_one_more_frame(a, name):
+    """after the replays, one eager frame that keeps its keyframe, audited from the runner's own state (tests/stream_audit.py):
+    correlation against float64, nothing written past the list, the operator stub, the inactive rows, gmap_pm == gmap -- in the
+    wrapped regime (patch table, patch and feature rings gone round, edge launches sized for the capacity)"""
+    aud = StreamAudit(name)
+    aud.arm(a)
+    a.frame(drop=False)
+    aud.audit(a)
+    aud.log("device_stream_wrapped_audit")
+    assert aud.counts["corr"] == 1 and aud.counts["bounds"] == 1 and aud.counts["inactive"] == 1
+    assert a.events.counts() == [0, 0, 0, 0]
 
 
 def test_device_stream_hipgraph_soak():
@@ -239,6 +267,7 @@ def test_device_stream_hipgraph_soak():
     assert a.E_inac == b.E_inac
     assert bool(torch.isfinite(a.poses[:n]).all())
     assert a.events.counts() == [0, 0, 0, 0] and b.events.counts() == [0, 0, 0, 0]
+    _audit_one_more_frame(a, "hipgraph_soak")
 
 
 def test_device_stream_outlives_its_frame_buffer_when_keyframes_are_dropped():
@@ -277,3 +306,32 @@ def test_device_stream_reports_a_capacity_error_instead_of_writing_past_it():
     blk = run.dyn[run.slot].cpu()
     assert (int(blk[0]), int(blk[1])) == (n0, E0) and int(blk[7]) == 1
     assert torch.equal(run._ii[run.cur, E0:E0 + 2000], guard)      # nothing was appended
+
+
+@pytest.mark.parametrize("cfg", [pytest.param(dict(buffer_size=512, keyframe_thresh=12.5, pose_step=0.1), id="M96"),
+                                 pytest.param(dict(M=196, opt_window=22, buffer_size=256, keyframe_thresh=12.5, pose_step=0.1),
+                                              id="M196-window22")])
+def test_device_stream_at_the_benchmarked_configurations(cfg):
+    """the two DeviceStreamRunner configurations bench.py --full times (384x512 frames; M = 96 at the default window, E ~ 40k,
+    and M = 196 with OPTIMIZATION_WINDOW 22, E ~ 80k): 45 frames to the steady state, then 40 with the reference's keyframe
+    test deciding on the device.  Every one of the 40 is audited from the runner's own state (tests/stream_audit.py: nothing
+    written past the list, operator stub, inactive rows, gmap_pm == gmap), and every 8th kept one also has its correlation
+    compared with float64 per level: that truth is a CPU call at E ~ 10^5, so only a few."""
+    import time
+    from cdv_slam_amd.stream import DeviceStreamRunner
+    run = DeviceStreamRunner(torch.device(DEV), **cfg)
+    aud = StreamAudit("M%d_window%d" % (run.M, run.ow), corr_every=8)
+    for f in range(45):
+        run.frame(drop=False)
+    t0 = time.perf_counter()
+    for f in range(40):
+        aud.arm(run)
+        run.frame(drop=None)
+        aud.audit(run)
+    t_audit = time.perf_counter() - t0
+    n, E = run.counts()
+    aud.log("device_stream_bench_config_audit")
+    print("40 audited frames in %.1f s, E = %d, %d keyframes" % (t_audit, E, n))
+    assert aud.counts["frames"] == 40 and aud.counts["bounds"] == 40 and aud.counts["inactive"] == 40 and aud.counts["corr"] >= 2
+    assert E > 30000 and aud.counts["pruned_rows"] > 0
+    assert run.events.counts() == [0, 0, 0, 0]
