@@ -25,10 +25,6 @@ SIGNATURES = {
     "cdv_fmap_ingest": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "cdv_corr_fused": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32,
                               _f32, _f32, _i32, _i64, _i64, _i32, _vp]),
-    "cdv_corr_fused_split": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32,
-                                    _f32, _f32, _i64, _i64, _i32, _vp]),
-    "cdv_corr_level_checked": (_i32, [_vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _i32, _i64, _i64, _i64, _i32, _i32, _i32, _f32,
-                                      _i64, _i64, _i32, _vp]),
     "cdv_corr_level_checked_interleaved": (_i32, [_vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _i32, _i64, _i64, _i64, _i32, _i32, _i32,
                                                   _f32, _i64, _i64, _i32, _vp]),
     "cdv_graph_workspace_init": (_i32, [_vp, _sz, _i64, _i64, _vp]),
@@ -56,7 +52,6 @@ SIGNATURES = {
     "cdv_fastba_reproject": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp]),
     "cdv_graph_workspace_bytes": (_sz, [_i64, _i64]),
     "cdv_graph_build": (_i32, [_vp, _vp, _i64, _vp, _sz, _i64, _i64, _vp]),
-    "cdv_graph_build_neighbors": (_i32, [_vp, _vp, _i64, _vp, _sz, _i64, _i64, _vp, _vp, _vp]),
     "cdv_graph_build_edges": (_i32, [_vp, _vp, _vp, _i64, _vp, _sz, _i64, _i64, _vp, _vp, _vp]),
     "cdv_graph_build_table": (_i32, [_vp, _vp, _vp, _i64, _vp, _sz, _i64, _i64, _i64, _vp, _vp, _vp]),
     "cdv_graph_table_offsets": (_i32, [_i64, _i64, _vp]),

@@ -9,7 +9,6 @@
 //                                (diagonal blocks), tile owners (Schur products on the matrix cores), blocked multi-workgroup
 //                                Cholesky, retract -- one owner and a fixed order for every sum here too (see below)
 //   N = 0           ba_patch_kernel + q + retract: depths alone.
-#include <stdlib.h>
 
 #include <atomic>
 #include <mutex>
@@ -634,351 +633,6 @@ __global__ __launch_bounds__(256) void ba_big_fold_kernel(float* __restrict__ sy
   }
 }
 
-// 16x16 tiles of X Y^T for two 64x64 blocks in LDS (row stride CLD), K = 64: tile (ti, tj) -> lane (c16, g4) holds
-// rows 16 ti + 4 g4 + q, column 16 tj + c16
-constexpr int CLD = CNB + 4;
-__device__ __forceinline__ cdv_float4 tile64_xyt(const float* X, const float* Y, int ti, int tj, int c16, int g4) {
-  const float* pa = X + (size_t)(16 * ti + c16) * CLD;
-  const float* pb = Y + (size_t)(16 * tj + c16) * CLD;
-  // (lane group g4 takes columns 16 g4 .. 16 g4 + 15: four 16-byte reads per operand; rows are 16-byte aligned, CLD = 68)
-  cdv_float4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int s4 = 0; s4 < 4; s4++) {
-    const int k = 16 * g4 + 4 * s4;
-    const cdv_float4 av = *reinterpret_cast<const cdv_float4*>(pa + k);
-    const cdv_float4 bv = *reinterpret_cast<const cdv_float4*>(pb + k);
-    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[0], bv[0], acc0, 0, 0, 0);
-    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[1], bv[1], acc1, 0, 0, 0);
-    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[2], bv[2], acc0, 0, 0, 0);
-    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[3], bv[3], acc1, 0, 0, 0);
-  }
-  return acc0 + acc1;
-}
-
-// Block step kb, part 1.  One wave per workgroup, lane = matrix row.  Every workgroup factors the 64x64 diagonal block
-// in its registers (redundantly; the single-wave scheme of ba_win.hip's solver: columns broadcast through LDS one ahead,
-// v_pk_fma_f32 rank-1 updates, no barrier) and parks L_kk in LDS; workgroup 0 writes it back; workgroup b > 0 solves its 64 rows of
-// the panel, X L_kk^T = A, by forward substitution along the row (L entries as LDS broadcast reads, 16 bytes at a
-// time); the last workgroup does the same for the right-hand-side row.
-__global__ __launch_bounds__(64) void ba_big_panel_kernel(float* __restrict__ A, int npad, int kb,
-                                                          const int32_t* __restrict__ gmeta, int32_t* __restrict__ info) {
-  if (gmeta[GM_ERROR] || info[1]) return;
-  __shared__ __attribute__((aligned(16))) float Ls[CNB * CLD];   // L_kk, row stride CLD (16-byte aligned rows)
-  typedef float cdv_float2 __attribute__((ext_vector_type(2)));
-  const int lane = threadIdx.x;
-  const int nb = npad / CNB;
-  const int rb = kb + blockIdx.x;               // block row handled here; rb == nb: the right-hand-side row
-  const size_t lda = (size_t)npad;
-  const int c0 = CNB * kb;
-  // ---- diagonal block: row `lane`, columns 0..63 -------------------------------------------------------
-  cdv_float2 a2[CNB / 2];
-  {
-    const float* src = A + (size_t)(c0 + lane) * lda + c0;
-#pragma unroll
-    for (int c4 = 0; c4 < CNB / 4; c4++) {
-      const cdv_float4 q = *reinterpret_cast<const cdv_float4*>(src + 4 * c4);
-      a2[2 * c4] = cdv_float2{q[0], q[1]};
-      a2[2 * c4 + 1] = cdv_float2{q[2], q[3]};
-    }
-  }
-  // this workgroup's own row of the panel (unused by workgroup 0), requested now
-  const bool rhs = rb == nb;
-  float* rowp = A + (size_t)(rhs ? npad : CNB * min(rb, nb - 1) + lane) * lda + c0;
-  float x[CNB];
-#pragma unroll
-  for (int c4 = 0; c4 < CNB / 4; c4++) {
-    const cdv_float4 q = *reinterpret_cast<const cdv_float4*>(rowp + 4 * c4);
-    x[4 * c4] = q[0]; x[4 * c4 + 1] = q[1]; x[4 * c4 + 2] = q[2]; x[4 * c4 + 3] = q[3];
-  }
-  // right-looking Cholesky in the wave's registers, column k broadcast through LDS ONE COLUMN AHEAD of its rank-1 update
-  // (the scheme of ba_win.hip's solver: a v_readlane costs ~16 cycles of issue, so only the chain -- L[k+1][k] and the next
-  // pivot -- travels that way; 2 x 2,016 of them made this kernel 21.7 us)
-  __shared__ __attribute__((aligned(16))) float colb[CNB];
-  bool bad = false;
-  float Lk;
-  {
-    const float piv = readlane_f(a2[0][0], 0);
-    bad = !(piv > 0.f);
-    Lk = a2[0][0] * __builtin_amdgcn_rsqf(piv);
-    a2[0][0] = Lk;
-    colb[lane] = Lk;
-  }
-  cdv_float2 bcur[CNB / 2], bnxt[CNB / 2];   // column k / column k + 1 of L, the same in every lane (pairs of columns)
-#pragma unroll
-  for (int c4 = 0; c4 < CNB / 4; c4++) {
-    const cdv_float4 v = *reinterpret_cast<const cdv_float4*>(&colb[4 * c4]);
-    bcur[2 * c4] = cdv_float2{v[0], v[1]};
-    bcur[2 * c4 + 1] = cdv_float2{v[2], v[3]};
-  }
-#pragma unroll
-  for (int k = 0; k < CNB; k++) {
-    float Ln = 0.f;
-    if (k + 1 < CNB) {
-      // column k + 1 first: its one update from column k, pivot, scale, broadcast request
-      const float an = fmaf(-Lk, readlane_f(Lk, k + 1), a2[(k + 1) >> 1][(k + 1) & 1]);
-      const float piv = readlane_f(an, k + 1);
-      bad = bad || !(piv > 0.f);                          // wave-uniform
-      Ln = an * __builtin_amdgcn_rsqf(piv);
-      a2[(k + 1) >> 1][(k + 1) & 1] = Ln;
-      colb[lane] = Ln;      // in-order LDS: the reads of column k were issued before this write
-#pragma unroll
-      for (int c4 = (k + 2) / 4; c4 < CNB / 4; c4++) {
-        const cdv_float4 v = *reinterpret_cast<const cdv_float4*>(&colb[4 * c4]);
-        bnxt[2 * c4] = cdv_float2{v[0], v[1]};
-        bnxt[2 * c4 + 1] = cdv_float2{v[2], v[3]};
-      }
-    }
-    // the rest of column k's rank-1 update (columns k + 2 ..) runs while column k + 1 travels through LDS
-    if (((k + 2) & 1) && k + 2 < CNB)
-      a2[(k + 2) >> 1][1] = fmaf(-Lk, bcur[(k + 2) >> 1][1], a2[(k + 2) >> 1][1]);
-    const cdv_float2 nLk = {-Lk, -Lk};
-#pragma unroll
-    for (int pp = (k + 3) >> 1; pp < CNB / 2; pp++) a2[pp] = __builtin_elementwise_fma(nLk, bcur[pp], a2[pp]);
-    Lk = Ln;
-#pragma unroll
-    for (int pp = (k + 2) >> 1; pp < CNB / 2; pp++) bcur[pp] = bnxt[pp];
-  }
-  // L_kk -> LDS (zeros above the diagonal), and back to the matrix from workgroup 0
-#pragma unroll
-  for (int c4 = 0; c4 < CNB / 4; c4++) {
-    cdv_float4 q;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-      const int c = 4 * c4 + j;
-      q[j] = (c <= lane) ? a2[c >> 1][c & 1] : 0.f;
-    }
-    *reinterpret_cast<cdv_float4*>(&Ls[lane * CLD + 4 * c4]) = q;
-    if (blockIdx.x == 0) {
-      float* dst = A + (size_t)(c0 + lane) * lda + c0 + 4 * c4;
-#pragma unroll
-      for (int j = 0; j < 4; j++)
-        if (4 * c4 + j <= lane) dst[j] = q[j];
-    }
-  }
-  if (blockIdx.x == 0) {
-    if (lane == 0 && bad && info[BI_CHOL] == 0) ba_flag(info, BI_CHOL, kb + 1);
-    return;
-  }
-  wave_lds_sync();
-  // ---- this workgroup's rows of the panel: x L^T = a, c = 0..63 in turn (the row was requested before the
-  // factorisation: its memory round trip ran underneath) -----------------------------------------------------
-  if (rhs && lane > 0) return;                    // the right-hand side is one row
-#pragma unroll
-  for (int c = 0; c < CNB; c++) {
-    float sacc = x[c];
-#pragma unroll
-    for (int j4 = 0; j4 < (c + 3) / 4; j4++) {      // L[c][4 j4 .. 4 j4 + 3]: one broadcast read of 16 bytes
-      const cdv_float4 l = *reinterpret_cast<const cdv_float4*>(&Ls[c * CLD + 4 * j4]);
-#pragma unroll
-      for (int j = 0; j < 4; j++)
-        if (4 * j4 + j < c) sacc = fmaf(-x[4 * j4 + j], l[j], sacc);
-    }
-    x[c] = sacc / Ls[c * CLD + c];
-  }
-#pragma unroll
-  for (int c4 = 0; c4 < CNB / 4; c4++)
-    *reinterpret_cast<cdv_float4*>(rowp + 4 * c4) = cdv_float4{x[4 * c4], x[4 * c4 + 1], x[4 * c4 + 2], x[4 * c4 + 3]};
-}
-
-// Block step kb >= 1 as ONE launch, the trailing update delayed by a step: what step kb - 1 owes the matrix is applied
-//   * to block column kb by the panel workgroups themselves, each to its own block and (redundantly) to the diagonal block,
-//     on the matrix cores, straight into the LDS the panel wave then reads its rows from;
-//   * to the blocks right of column kb by update workgroups, as in ba_big_update_kernel;
-// both need only panel kb - 1 (the previous launch) and touch disjoint blocks, so the panel chain of step kb (one wave,
-// ~18 us) no longer waits for a trailing-update launch of its own: 29 x (20 + 14.5 us + two launch gaps) became 29 x ~23.
-// Workgroups 0 .. nb - kb: panel (0 = diagonal block, last = the right-hand-side row); the rest: updates.
-constexpr int STEP_T = 512;   // threads of a step workgroup: eight waves share the 16 (update) or 32 (panel) tiles
-__global__ __launch_bounds__(STEP_T) void ba_big_step_kernel(float* __restrict__ A, int npad, int kb,
-                                                             const int32_t* __restrict__ gmeta, int32_t* __restrict__ info) {
-  if (gmeta[GM_ERROR] || info[1]) return;
-  __shared__ __attribute__((aligned(16))) float Pr[CNB * CLD];
-  __shared__ __attribute__((aligned(16))) float Pc[CNB * CLD];
-  __shared__ __attribute__((aligned(16))) float Ls[CNB * CLD];
-  __shared__ __attribute__((aligned(16))) float colb[CNB];
-  typedef float cdv_float2 __attribute__((ext_vector_type(2)));
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, c16 = lane & 15, g4 = lane >> 4;
-  const int nb = npad / CNB;
-  const size_t lda = (size_t)npad;
-  const int c0 = CNB * kb, cp = CNB * (kb - 1);   // columns of this step's panel / of the panel whose update is due
-  const int nA = nb - kb + 1;
-  if ((int)blockIdx.x >= nA) {
-    // ---- update role: block (rb, cb), cb > kb, or the right-hand-side row against column block cb ----
-    const int idx = (int)blockIdx.x - nA;
-    const int T = nb - kb - 1;
-    const int ntri = T * (T + 1) / 2;
-    int rb, cb;
-    bool rhs = false;
-    if (idx < ntri) {
-      int ri = 0, ar = 0;
-      while (ar + ri + 1 <= idx) { ar += ri + 1; ri++; }
-      rb = kb + 1 + ri; cb = kb + 1 + (idx - ar);
-    } else {
-      rhs = true; rb = nb; cb = kb + 1 + (idx - ntri);
-    }
-    for (int i = t; i < CNB * CNB; i += STEP_T) {
-      const int r = i >> 6, c = i & 63;
-      Pr[r * CLD + c] = rhs ? (r == 0 ? A[(size_t)npad * lda + cp + c] : 0.f) : A[(size_t)(CNB * rb + r) * lda + cp + c];
-      Pc[r * CLD + c] = A[(size_t)(CNB * cb + r) * lda + cp + c];
-    }
-    __syncthreads();
-    for (int tix = wave; tix < 16; tix += STEP_T / 64) {
-      const int ti = tix >> 2, tj = tix & 3;
-      const cdv_float4 acc = tile64_xyt(Pr, Pc, ti, tj, c16, g4);
-#pragma unroll
-      for (int q = 0; q < 4; q++) {
-        const int r = 16 * ti + 4 * g4 + q, c = 16 * tj + c16;
-        if (rhs) {
-          if (r == 0) A[(size_t)npad * lda + CNB * cb + c] -= acc[q];
-        } else {
-          A[(size_t)(CNB * rb + r) * lda + CNB * cb + c] -= acc[q];
-        }
-      }
-    }
-    return;
-  }
-  // ---- panel role ----
-  const int rb = kb + (int)blockIdx.x;          // block row handled here; rb == nb: the right-hand-side row
-  const bool rhs = rb == nb;
-  const bool diag = blockIdx.x == 0;
-  // panel kb - 1: this workgroup's rows (Pr) and the rows of block row kb (Pc); and, in the same round trip, the entries of
-  // the own block and of the diagonal block this wave's tiles will be subtracted from
-  constexpr int TU = 16 / (STEP_T / 64);   // tiles of each of the two blocks per wave
-  float o[TU][4], d[TU][4];
-#pragma unroll
-  for (int u = 0; u < TU; u++) {
-    const int tix = wave + (STEP_T / 64) * u, ti = tix >> 2, tj = tix & 3;
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-      const int r = 16 * ti + 4 * g4 + q, c = 16 * tj + c16;
-      o[u][q] = rhs ? (r == 0 ? A[(size_t)npad * lda + c0 + c] : 0.f) : A[(size_t)(CNB * rb + r) * lda + c0 + c];
-      d[u][q] = A[(size_t)(c0 + r) * lda + c0 + c];
-    }
-  }
-  for (int i = t; i < CNB * CNB; i += STEP_T) {
-    const int r = i >> 6, c = i & 63;
-    Pr[r * CLD + c] = rhs ? (r == 0 ? A[(size_t)npad * lda + cp + c] : 0.f) : A[(size_t)(CNB * rb + r) * lda + cp + c];
-    Pc[r * CLD + c] = A[(size_t)(CNB * kb + r) * lda + cp + c];
-  }
-  __syncthreads();
-  // the 16 tiles of the own block and the 16 of the diagonal block, dealt to the waves: products in registers ...
-  cdv_float4 own[TU], dia[TU];
-#pragma unroll
-  for (int u = 0; u < TU; u++) {
-    const int tix = wave + (STEP_T / 64) * u, ti = tix >> 2, tj = tix & 3;
-    own[u] = tile64_xyt(Pr, Pc, ti, tj, c16, g4);
-    dia[u] = tile64_xyt(Pc, Pc, ti, tj, c16, g4);
-  }
-  __syncthreads();   // everybody is done reading the panels
-  // ... subtracted from the blocks, the results parked where the panels were: Pr <- own block (the right-hand side: its
-  // row 0), Pc <- diagonal block
-#pragma unroll
-  for (int u = 0; u < TU; u++) {
-    const int tix = wave + (STEP_T / 64) * u, ti = tix >> 2, tj = tix & 3;
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-      const int r = 16 * ti + 4 * g4 + q, c = 16 * tj + c16;
-      Pr[r * CLD + c] = o[u][q] - own[u][q];
-      Pc[r * CLD + c] = d[u][q] - dia[u][q];
-    }
-  }
-  __syncthreads();
-  if (wave != 0) return;
-  // ---- from here on: ba_big_panel_kernel's single wave, its rows read from LDS ----
-  cdv_float2 a2[CNB / 2];
-#pragma unroll
-  for (int c4 = 0; c4 < CNB / 4; c4++) {
-    const cdv_float4 q = *reinterpret_cast<const cdv_float4*>(&Pc[lane * CLD + 4 * c4]);
-    a2[2 * c4] = cdv_float2{q[0], q[1]};
-    a2[2 * c4 + 1] = cdv_float2{q[2], q[3]};
-  }
-  float* rowp = A + (size_t)(rhs ? npad : CNB * min(rb, nb - 1) + lane) * lda + c0;
-  float x[CNB];
-#pragma unroll
-  for (int c4 = 0; c4 < CNB / 4; c4++) {
-    const cdv_float4 q = *reinterpret_cast<const cdv_float4*>(&Pr[(rhs ? 0 : lane) * CLD + 4 * c4]);
-    x[4 * c4] = q[0]; x[4 * c4 + 1] = q[1]; x[4 * c4 + 2] = q[2]; x[4 * c4 + 3] = q[3];
-  }
-  bool bad = false;
-  float Lk;
-  {
-    const float piv = readlane_f(a2[0][0], 0);
-    bad = !(piv > 0.f);
-    Lk = a2[0][0] * __builtin_amdgcn_rsqf(piv);
-    a2[0][0] = Lk;
-    colb[lane] = Lk;
-  }
-  cdv_float2 bcur[CNB / 2], bnxt[CNB / 2];
-#pragma unroll
-  for (int c4 = 0; c4 < CNB / 4; c4++) {
-    const cdv_float4 v = *reinterpret_cast<const cdv_float4*>(&colb[4 * c4]);
-    bcur[2 * c4] = cdv_float2{v[0], v[1]};
-    bcur[2 * c4 + 1] = cdv_float2{v[2], v[3]};
-  }
-#pragma unroll
-  for (int k = 0; k < CNB; k++) {
-    float Ln = 0.f;
-    if (k + 1 < CNB) {
-      const float an = fmaf(-Lk, readlane_f(Lk, k + 1), a2[(k + 1) >> 1][(k + 1) & 1]);
-      const float piv = readlane_f(an, k + 1);
-      bad = bad || !(piv > 0.f);                          // wave-uniform
-      Ln = an * __builtin_amdgcn_rsqf(piv);
-      a2[(k + 1) >> 1][(k + 1) & 1] = Ln;
-      colb[lane] = Ln;
-#pragma unroll
-      for (int c4 = (k + 2) / 4; c4 < CNB / 4; c4++) {
-        const cdv_float4 v = *reinterpret_cast<const cdv_float4*>(&colb[4 * c4]);
-        bnxt[2 * c4] = cdv_float2{v[0], v[1]};
-        bnxt[2 * c4 + 1] = cdv_float2{v[2], v[3]};
-      }
-    }
-    if (((k + 2) & 1) && k + 2 < CNB)
-      a2[(k + 2) >> 1][1] = fmaf(-Lk, bcur[(k + 2) >> 1][1], a2[(k + 2) >> 1][1]);
-    const cdv_float2 nLk = {-Lk, -Lk};
-#pragma unroll
-    for (int pp = (k + 3) >> 1; pp < CNB / 2; pp++) a2[pp] = __builtin_elementwise_fma(nLk, bcur[pp], a2[pp]);
-    Lk = Ln;
-#pragma unroll
-    for (int pp = (k + 2) >> 1; pp < CNB / 2; pp++) bcur[pp] = bnxt[pp];
-  }
-#pragma unroll
-  for (int c4 = 0; c4 < CNB / 4; c4++) {
-    cdv_float4 q;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-      const int c = 4 * c4 + j;
-      q[j] = (c <= lane) ? a2[c >> 1][c & 1] : 0.f;
-    }
-    *reinterpret_cast<cdv_float4*>(&Ls[lane * CLD + 4 * c4]) = q;
-    if (diag) {
-      float* dst = A + (size_t)(c0 + lane) * lda + c0 + 4 * c4;
-#pragma unroll
-      for (int j = 0; j < 4; j++)
-        if (4 * c4 + j <= lane) dst[j] = q[j];
-    }
-  }
-  if (diag) {
-    if (lane == 0 && bad && info[BI_CHOL] == 0) ba_flag(info, BI_CHOL, kb + 1);
-    return;
-  }
-  wave_lds_sync();
-  if (rhs && lane > 0) return;                    // the right-hand side is one row
-#pragma unroll
-  for (int c = 0; c < CNB; c++) {
-    float sacc = x[c];
-#pragma unroll
-    for (int j4 = 0; j4 < (c + 3) / 4; j4++) {
-      const cdv_float4 l = *reinterpret_cast<const cdv_float4*>(&Ls[c * CLD + 4 * j4]);
-#pragma unroll
-      for (int j = 0; j < 4; j++)
-        if (4 * j4 + j < c) sacc = fmaf(-x[4 * j4 + j], l[j], sacc);
-    }
-    x[c] = sacc / Ls[c * CLD + c];
-  }
-#pragma unroll
-  for (int c4 = 0; c4 < CNB / 4; c4++)
-    *reinterpret_cast<cdv_float4*>(rowp + 4 * c4) = cdv_float4{x[4 * c4], x[4 * c4 + 1], x[4 * c4 + 2], x[4 * c4 + 3]};
-}
-
 // L^T x = z as ONE launch of one-wave workgroups, one per 64-column block (round 5; until then 256-column workgroups with four
 // barriers and an LDS exchange per step: 12.8k cycles a step, of which 5.0k went into ISSUING 64 four-byte row loads per
 // thread -- a wave cannot have more than 64 vector loads outstanding -- in front of the block solve instead of under it).
@@ -1365,7 +1019,6 @@ static int ba_forward_impl(float* poses, float* patches, const float* intrinsics
   const int n_chunks = cdv_div_up(L.U_max, BA_CHUNK);
   const int rb = cdv_div_up(L.U_max > N ? L.U_max : N, 64);
   const int npad = (int)L.npad, nbk = npad / CNB;
-  static const bool block_steps = []() { const char* e = getenv("CDV_BA_BLOCK_STEPS"); return e && e[0] == '1'; }();
   if (big) {
     // the frame-pair index of this call's edges (both iterations use it): keys, an ordinary index build over them, the
     // (a, b) -> pair table
@@ -1402,20 +1055,9 @@ static int ba_forward_impl(float* poses, float* patches, const float* intrinsics
                          (int)L.U_stride, cmask, n_chunks, info);
       hipLaunchKernelGGL(ba_big_fold_kernel, dim3(1024), dim3(256), 0, s, sy, (int)L.sy_stride, n6i, npad, Abig, gv.meta,
                          d, info, (uint64_t*)(b + L.xgran), (int32_t*)(b + L.fctl), fac_ctl_words(nbk));
-      if (!block_steps) {
-        // the factorisation as one launch of block work items (ba_factor.hip)
-        const int rcf = cdv_ba_big_factor(Abig, npad, (int32_t*)(b + L.fctl), (float*)(b + L.ltg), gv.meta, info, g_handoff_test.load(), s);
-        if (rcf != CDV_OK) return rcf;
-      } else {
-        // (rounds 1-3, kept for comparison: CDV_BA_BLOCK_STEPS=1) one launch per block column.  Block step 0: the panel alone;
-        // block step kb >= 1: the panel together with what step kb - 1 owes the matrix
-        hipLaunchKernelGGL(ba_big_panel_kernel, dim3(nbk + 1), dim3(64), 0, s, Abig, npad, 0, gv.meta, info);
-        for (int kb = 1; kb < nbk; kb++) {
-          const int T = nbk - kb - 1;
-          hipLaunchKernelGGL(ba_big_step_kernel, dim3(nbk - kb + 1 + T * (T + 1) / 2 + T), dim3(STEP_T), 0, s, Abig, npad, kb, gv.meta,
-                             info);
-        }
-      }
+      // the factorisation as one launch of block work items (ba_factor.hip)
+      const int rcf = cdv_ba_big_factor(Abig, npad, (int32_t*)(b + L.fctl), (float*)(b + L.ltg), gv.meta, info, g_handoff_test.load(), s);
+      if (rcf != CDV_OK) return rcf;
       hipLaunchKernelGGL(ba_big_backsolve_kernel, dim3(npad / CNB), dim3(64), 0, s, Abig, npad, n6i, dXg,
                          (uint64_t*)(b + L.xgran), token_base + 1 + itr, gv.meta, d, info, g_handoff_test.load());
     } else {

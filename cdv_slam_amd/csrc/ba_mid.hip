@@ -22,7 +22,6 @@
 //                           panels of 24 columns factored inside single waves (one matrix row per lane, pivots and
 //                           L[m][k] by v_readlane), trailing update as 16 x 16 tiles on the matrix cores (K = 24), back
 //                           substitution inside one wave.
-#include <stdlib.h>
 
 #include "cdv_ba_pairs.h"
 
@@ -41,6 +40,7 @@ constexpr int SC = 2;
 constexpr int CKS = SC * CK;               // patches per workgroup
 constexpr int EDL = CKS + 1;               // row stride of the wide chunk's [E; u] block in LDS
 constexpr int FT = 512;                    // threads of a finish workgroup
+constexpr int MKW = 8;                     // waves of a chunk workgroup (cdv_ba_mid_iteration has the measurements)
 
 // ---- footprint of a chunk in B and v, per wave --------------------------------------------------------------------
 //   [0, 54)                   F_ii[s]   s = 0, 1: 21 (B_ii lower triangle) + 6 (v_i) of source slot s
@@ -82,11 +82,6 @@ __device__ __forceinline__ int nth_bit(uint32_t m, int k) {
   return m ? __ffs((int)m) - 1 : -1;
 }
 
-#ifdef CDV_MID_WPE
-#define CDV_MID_OCC __attribute__((amdgpu_waves_per_eu(CDV_MID_WPE, CDV_MID_WPE)))
-#else
-#define CDV_MID_OCC
-#endif
 // Rows of wide chunk wc: plainly [CKS wc, + CKS); with A.ppf > 0 (a patch table whose capacity is a multiple of the patches per
 // frame: a frame's patches then sit in ppf consecutive slots) the wide chunks are cut PER FRAME -- pieces of CKS rows, the
 // last one shorter -- so that no workgroup holds patches of two source frames: a row of 16 lanes whose patches belong to two
@@ -109,8 +104,8 @@ __device__ __forceinline__ int wide_count(const BaWinArgs& A, int U) {
   return ((U + CK - 1) / CK + SC - 1) / SC;
 }
 
-template <bool HAS_II, int MKW, bool TABLE>
-__global__ __launch_bounds__(64 * MKW) CDV_MID_OCC void ba_mid_chunk_kernel(BaWinArgs A_in) {
+template <bool HAS_II, bool TABLE>
+__global__ __launch_bounds__(64 * MKW) void ba_mid_chunk_kernel(BaWinArgs A_in) {
   const BaWinArgs A = with_dyn(A_in);   // (a frame stream's window lives on the device: every layout below follows ITS N)
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int N = A.N, t0 = A.t0, P = A.P;
@@ -1143,16 +1138,16 @@ __global__ __launch_bounds__(FT) void ba_mid_finish_kernel(BaWinArgs A_in) {
   }
 }
 
-template <bool HAS_II, int MKW, bool TABLE>
+template <bool HAS_II, bool TABLE>
 hipError_t chunk_attr() {
-  return hipFuncSetAttribute((const void*)ba_mid_chunk_kernel<HAS_II, MKW, TABLE>, hipFuncAttributeMaxDynamicSharedMemorySize,
+  return hipFuncSetAttribute((const void*)ba_mid_chunk_kernel<HAS_II, TABLE>, hipFuncAttributeMaxDynamicSharedMemorySize,
                              160 * 1024 - 256);
 }
 
-template <int MKW, bool TABLE>
+template <bool TABLE>
 void launch_chunk(const BaWinArgs& a, int grid, size_t lds, hipStream_t s) {
-  if (a.has_ii) hipLaunchKernelGGL((ba_mid_chunk_kernel<true, MKW, TABLE>), dim3(grid), dim3(64 * MKW), lds, s, a);
-  else hipLaunchKernelGGL((ba_mid_chunk_kernel<false, MKW, TABLE>), dim3(grid), dim3(64 * MKW), lds, s, a);
+  if (a.has_ii) hipLaunchKernelGGL((ba_mid_chunk_kernel<true, TABLE>), dim3(grid), dim3(64 * MKW), lds, s, a);
+  else hipLaunchKernelGGL((ba_mid_chunk_kernel<false, TABLE>), dim3(grid), dim3(64 * MKW), lds, s, a);
 }
 
 template <int SNP, bool TABLE>
@@ -1174,18 +1169,10 @@ int cdv::cdv_ba_mid_wide_per_frame(int ppf) { return wide_per_frame(ppf); }
 int cdv::cdv_ba_mid_iteration(const BaWinArgs& a, hipStream_t s) {
   static hipError_t attr_err = [] {
     hipError_t e = hipSuccess, x;
-    if ((x = chunk_attr<true, 8, false>()) != hipSuccess) e = x;
-    if ((x = chunk_attr<false, 8, false>()) != hipSuccess) e = x;
-    if ((x = chunk_attr<true, 8, true>()) != hipSuccess) e = x;
-    if ((x = chunk_attr<false, 8, true>()) != hipSuccess) e = x;
-    if ((x = chunk_attr<true, 7, false>()) != hipSuccess) e = x;
-    if ((x = chunk_attr<false, 7, false>()) != hipSuccess) e = x;
-    if ((x = chunk_attr<true, 7, true>()) != hipSuccess) e = x;
-    if ((x = chunk_attr<false, 7, true>()) != hipSuccess) e = x;
-    if ((x = chunk_attr<true, 4, false>()) != hipSuccess) e = x;
-    if ((x = chunk_attr<false, 4, false>()) != hipSuccess) e = x;
-    if ((x = chunk_attr<true, 4, true>()) != hipSuccess) e = x;
-    if ((x = chunk_attr<false, 4, true>()) != hipSuccess) e = x;
+    if ((x = chunk_attr<true, false>()) != hipSuccess) e = x;
+    if ((x = chunk_attr<false, false>()) != hipSuccess) e = x;
+    if ((x = chunk_attr<true, true>()) != hipSuccess) e = x;
+    if ((x = chunk_attr<false, true>()) != hipSuccess) e = x;
     if ((x = finish_attr<96, false>()) != hipSuccess) e = x;
     if ((x = finish_attr<144, false>()) != hipSuccess) e = x;
     if ((x = finish_attr<192, false>()) != hipSuccess) e = x;
@@ -1198,26 +1185,15 @@ int cdv::cdv_ba_mid_iteration(const BaWinArgs& a, hipStream_t s) {
   const int N = a.N;
   // 8 waves per chunk workgroup: 32 target slots per round.  (The kernel needs ~250 VGPRs, so a CU holds 8 of its waves
   // whatever the split.  Workgroups of 4 waves, two per CU -- so that the stress configuration's 294 chunks are resident at
-  // once instead of taking a second round of 38 workgroups -- were measured: 49.1 against 41.7 us; the kernel is written
-  // for either, CDV_MID_WAVES=4 selects them.)
+  // once instead of taking a second round of 38 workgroups -- were measured: 49.1 against 41.7 us; seven waves: 43.0.)
   const int n_wide = a.ppf > 0 ? (a.tab_cap / a.ppf) * wide_per_frame(a.ppf) : cdv_div_up(a.n_ck_cap, SC);
   CDV_REQUIRE(n_wide <= a.n_ck_cap, CDV_ERR_WORKSPACE, "cdv_ba_forward: more wide chunks than slabs in the workspace");   // (ba.hip drops the hint before)
   const int n_ck = n_wide < WIN_MAX_GRID ? n_wide : WIN_MAX_GRID;
   const bool table = a.tab_cap > 0;
-  static const int mkw_env = getenv("CDV_MID_WAVES") ? atoi(getenv("CDV_MID_WAVES")) : 8;
-  const int mkw = mkw_env == 4 ? 4 : (mkw_env == 7 ? 7 : 8);
-  const size_t lds = chunk_lds_bytes(N, mkw);
+  const size_t lds = chunk_lds_bytes(N, MKW);
   CDV_REQUIRE(lds <= 160 * 1024 - 256, CDV_ERR_UNSUPPORTED, "cdv_ba_forward: chunk footprint exceeds LDS");
-  if (mkw == 8) {
-    if (table) launch_chunk<8, true>(a, n_ck, lds, s);
-    else launch_chunk<8, false>(a, n_ck, lds, s);
-  } else if (mkw == 7) {
-    if (table) launch_chunk<7, true>(a, n_ck, lds, s);
-    else launch_chunk<7, false>(a, n_ck, lds, s);
-  } else {
-    if (table) launch_chunk<4, true>(a, n_ck, lds, s);
-    else launch_chunk<4, false>(a, n_ck, lds, s);
-  }
+  if (table) launch_chunk<true>(a, n_ck, lds, s);
+  else launch_chunk<false>(a, n_ck, lds, s);
   const int n = 6 * N;
   {
     const int S4 = mid_slab(N) / 4;

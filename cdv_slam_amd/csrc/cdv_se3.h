@@ -28,11 +28,7 @@ template <typename T> __device__ __forceinline__ T t_atan(T x);
 template <> __device__ __forceinline__ float t_atan<float>(float x) { return atanf(x); }
 template <> __device__ __forceinline__ double t_atan<double>(double x) { return atan(x); }
 
-#ifdef CDV_EXP_CONTRACT
-#define CDV_NOCONTRACT
-#else
 #define CDV_NOCONTRACT _Pragma("clang fp contract(off)")
-#endif
 
 template <typename T>
 __device__ __forceinline__ void cross3(const T* a, const T* b, T* o) {

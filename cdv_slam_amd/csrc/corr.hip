@@ -55,15 +55,8 @@ constexpr int NQ_MAX = 8;                       // 16-pixel groups of the densel
 // conflicted: 112 of 296 LDS cycles per edge)
 constexpr int RAW_MSH = RAW_ROWS * 16 + 12;
 constexpr int RAW_HALFS = 9 * RAW_MSH;          // 1836
-#ifndef CDV_CORR_WAVES
-#define CDV_CORR_WAVES 4        // waves (= edges) per workgroup of the product kernel; the waves are independent (no barrier)
-#endif
-#ifndef CDV_CORR_EPW
-#define CDV_CORR_EPW 1          // edges per wave (packed-stream instance only): > 1 requests the next record under the current edge
-#endif
-#ifndef CDV_CORR_OUT_POLICY
-#define CDV_CORR_OUT_POLICY 16   // cache policy of the product kernel's output stores: 0 plain, 16 sc1 (write-through), 2 nt
-#endif
+constexpr int CW = 4;                           // waves (= edges) per workgroup of the product kernel; the waves are independent (no barrier)
+constexpr int OUT_POLICY = 16;                  // cache policy of the product kernel's output stores: sc1 (write-through)
 constexpr int OUT_HALFS = 896;                  // the staged output row: 882 halfs, linear (the copy-out needs no index math)
 constexpr int WAVE_LDS_BYTES = RAW_HALFS * 2 + OUT_HALFS * 2;  // wide kernel: raw volume + staged row
 // product kernel: the staged row re-uses the raw volume (written after the last blend has read it); the D-tile lanes
@@ -482,13 +475,10 @@ struct CorrArgs2 {
   int exp;
   // one-level launches only: output element (e, t) at out[e * out_pitch + t * out_stride + out_off] (inside the row of a
   // two-level result), and edges whose coordinates equal coords_ref * ref_mul bit for bit are skipped (their values are
-  // in place already: cdv_corr_level_checked)
+  // in place already: cdv_corr_level_checked_interleaved)
   int out_stride, out_off, out_pitch;   // out_pitch: halves from one edge's row to the next
   const float* coords_ref;
   float ref_mul;
-  // two-level launches: != 0 keeps the levels apart, [E][2][442] halves (row 884 B: each level a contiguous run of 441 --
-  // what two separate one-level results look like to torch.stack) instead of [E][441][2]
-  int split;
   // packed per-edge input stream in PROCESSING order (written by the index build next to `order`): record p =
   // {18 coords, edge id, patch-ring index, frame-ring index (0xFFFFFFFF: invalid), ...} -- cdv_graph.h CORR_REC_WORDS
   const uint32_t* rec;
@@ -513,17 +503,9 @@ struct EdgeCoords {
   int ixmin, ixmax, iymin, iymax;
 };
 
-// the wave's NEXT record, requested inside corr_edge behind the level-0 window loads (experiment builds with more than one
-// edge per wave, CDV_CORR_EPW): two gathers for this lane's blend coordinates, the record's scalar words as scalar loads
-struct NextRec {
-  float xb, yb;
-  uint32_t w18, w19, w20, w21, w22;
-};
-
-template <int CC, int NLEV, bool SPLIT, bool REC>
+template <int CC, int NLEV, bool REC>
 __device__ __forceinline__ void corr_edge(const CorrArgs2& a, int p, int e, const EdgeCoords& ec, uint32_t kq, uint32_t jq,
-                                          bool idx_ok, int lane, _Float16* __restrict__ raw, _Float16* __restrict__ outT,
-                                          const uint32_t* __restrict__ rnext = nullptr, NextRec* nx = nullptr) {
+                                          bool idx_ok, int lane, _Float16* __restrict__ raw, _Float16* __restrict__ outT) {
   CDV_STAMP(corr, p, 0);
   const int C = CC ? CC : a.C;
 #ifdef CDV_STAMPS
@@ -676,11 +658,6 @@ __device__ __forceinline__ void corr_edge(const CorrArgs2& a, int p, int e, cons
     }                                                                                              \
   }
   if (do0 && !CDV_EXP(1)) CDV2_LOAD_FIXED(b0, r0, pitch0, NQF0, nq0)
-  if (rnext) {   // (wave-uniform) behind the window request: the waits for the window data leave these in flight
-    nx->xb = __int_as_float((int)rnext[bm]);
-    nx->yb = __int_as_float((int)rnext[9 + bm]);
-    nx->w18 = rnext[18]; nx->w19 = rnext[19]; nx->w20 = rnext[20]; nx->w21 = rnext[21]; nx->w22 = rnext[22];
-  }
   const BlendGeo g0 = blend_geo(xb, yb, bm, bxo, L0, b0, !b0.fast);
   const BlendGeo g1 = blend_geo(xb, yb, bm, bxo, L1, b1, !b1.fast);
   CDV_STAMP(corr, p, 2);
@@ -724,11 +701,7 @@ __device__ __forceinline__ void corr_edge(const CorrArgs2& a, int p, int e, cons
   // ---- stage the edge's output row [x][y][m][lev] in LDS, then 16-byte-per-lane stores ------------------------------
   wave_lds_sync();   // the row overwrites the raw volume: keep the stores behind the last blend's reads
   if (lane < 63 && !CDV_EXP(512)) {
-    if (NLEV == 2 && SPLIT) {
-      _Float16* o0 = outT + __mul24(bxo, 63) + bm;   // half (x, y, m) = 63 x + 9 y + m; level 1 starts 442 halfs on
-#pragma unroll
-      for (int yo = 0; yo < 7; yo++) { o0[yo * 9] = res0[yo]; o0[442 + yo * 9] = res1[yo]; }
-    } else if (NLEV == 2) {
+    if (NLEV == 2) {
       uint32_t* o32 = reinterpret_cast<uint32_t*>(outT) + __mul24(bxo, 63) + bm;   // dword (x, y, m) = 63 x + 9 y + m (24-bit multiply: full rate)
 #pragma unroll
       for (int yo = 0; yo < 7; yo++) {
@@ -747,32 +720,20 @@ __device__ __forceinline__ void corr_edge(const CorrArgs2& a, int p, int e, cons
       // 441 dwords: two 16-byte-per-lane stores (256 + 184 dwords) and one last dword.  The row starts on a 4-byte
       // boundary only (1764 B per edge); global memory takes the unaligned 16-byte accesses.
       const uint32_t* src = reinterpret_cast<const uint32_t*>(outT);
-      uint32_t* dst = reinterpret_cast<uint32_t*>(a.out) + (size_t)e * (SPLIT ? 442 : 441);
+      uint32_t* dst = reinterpret_cast<uint32_t*>(a.out) + (size_t)e * 441;
       typedef uint32_t cdv_u32x4 __attribute__((ext_vector_type(4)));
-      typedef uint32_t cdv_u32x4u __attribute__((ext_vector_type(4), aligned(4)));
       const cdv_u32x4 v0 = *reinterpret_cast<const cdv_u32x4*>(src + 4 * lane);
-#if CDV_CORR_OUT_POLICY
       // the output row leaves written through (sc1: the line is dropped from this XCD's L2 instead of staying there -- 84 MB of
       // output per launch that nobody of this launch reads again pushed the feature maps out of the 4 MB L2s; round 5, measured
       // back to back on the default / stress workloads: 38.4-38.9 -> 37.6 us, 70.5-71.2 -> 69.2-69.4 us; nt (2): the same)
       typedef int cdv_i32x4s __attribute__((ext_vector_type(4)));
       const auto rso = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char*>(dst), (short)0, 1768, 0x00020000);
-      __builtin_amdgcn_raw_buffer_store_b128((cdv_i32x4s)v0, rso, 16 * lane, 0, CDV_CORR_OUT_POLICY);
+      __builtin_amdgcn_raw_buffer_store_b128((cdv_i32x4s)v0, rso, 16 * lane, 0, OUT_POLICY);
       if (lane < 46) {
         const cdv_u32x4 v1 = *reinterpret_cast<const cdv_u32x4*>(src + 256 + 4 * lane);
-        __builtin_amdgcn_raw_buffer_store_b128((cdv_i32x4s)v1, rso, 1024 + 16 * lane, 0, CDV_CORR_OUT_POLICY);
+        __builtin_amdgcn_raw_buffer_store_b128((cdv_i32x4s)v1, rso, 1024 + 16 * lane, 0, OUT_POLICY);
       }
-      if (lane == 63) __builtin_amdgcn_raw_buffer_store_b32((int)src[440], rso, 1760, 0, CDV_CORR_OUT_POLICY);
-      if (lane == 62 && SPLIT) __builtin_amdgcn_raw_buffer_store_b32((int)src[441], rso, 1764, 0, CDV_CORR_OUT_POLICY);
-#else
-      *reinterpret_cast<cdv_u32x4u*>(dst + 4 * lane) = v0;
-      if (lane < 46) {
-        const cdv_u32x4 v1 = *reinterpret_cast<const cdv_u32x4*>(src + 256 + 4 * lane);
-        *reinterpret_cast<cdv_u32x4u*>(dst + 256 + 4 * lane) = v1;
-      }
-      if (lane == 63) dst[440] = src[440];
-      if (lane == 62 && SPLIT) dst[441] = src[441];
-#endif
+      if (lane == 63) __builtin_amdgcn_raw_buffer_store_b32((int)src[440], rso, 1760, 0, OUT_POLICY);
     } else {
       _Float16* dst = a.out + (size_t)e * a.out_pitch + a.out_off;
 #pragma unroll
@@ -805,9 +766,7 @@ __device__ __forceinline__ bool ring_index(int64_t v64, uint32_t mod, uint32_t m
 // goes out with no kernel-argument load in front of it at all -- measured next to this build and to the one before it
 // (two dependent scalar round trips): 36.3-37.6 us back to back for all three, no difference.  The kernel is not bound by
 // the length of one wave's chain of round trips; the preload flag is not used.)
-constexpr int CW = CDV_CORR_WAVES;
-constexpr int EPW = CDV_CORR_EPW;
-template <int CC, int NLEV, bool SPLIT = false, bool REC = false>
+template <int CC, int NLEV, bool REC = false>
 __global__ __launch_bounds__(64 * CW) void corr_fused2_kernel(const uint32_t* __restrict__ rec_h, const int32_t* __restrict__ dynE_h,
                                                           int E_h, int eighth_h, const CorrArgs2 a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -816,49 +775,18 @@ __global__ __launch_bounds__(64 * CW) void corr_fused2_kernel(const uint32_t* __
   _Float16* raw = reinterpret_cast<_Float16*>(smem_raw + (size_t)wave * WAVE_LDS2_BYTES);
   _Float16* outT = raw;   // the staged output row takes the place of the raw volume once both blends are done
   // workgroup b runs on XCD b % 8 and takes CW consecutive edges of the b % 8-th contiguous eighth of the list.  (Round 5,
-  // CDV_CORR_EPW = 2 / 3 edges per wave with the next record requested behind the current edge's window loads: 77 registers
-  // instead of 62 (70 without machine LICM), six (seven) waves per SIMD instead of eight: 40.5 (39.3) against 37.7 us back to
-  // back -- the hidden round trip buys what the lost waves cost, no more; forced to 64 registers it spills 43 values: 79 us.
-  // Workgroups of 8 / 16 waves instead of 4: 1 % / 5 % slower.  Kept as build switches)
-  constexpr int KE = REC ? EPW : 1;
+  // 2 / 3 edges per wave with the next record requested behind the current edge's window loads: 77 registers instead of 62
+  // (70 without machine LICM), six (seven) waves per SIMD instead of eight: 40.5 (39.3) against 37.7 us back to back -- the
+  // hidden round trip buys what the lost waves cost, no more; forced to 64 registers it spills 43 values: 79 us.  Workgroups
+  // of 8 / 16 waves instead of 4: 1 % / 5 % slower.  DESIGN.md section 3.)
   int E = E_h, eighth = eighth_h;
   if (REC && dynE_h) {    // sizes on the device: the contiguous eighths are those of the ACTUAL list, not of the launch
     E = min(__builtin_amdgcn_readfirstlane(*dynE_h), E_h);
-    eighth = (E + 8 * CW * KE - 1) / (8 * CW * KE);
+    eighth = (E + 8 * CW - 1) / (8 * CW);
     if (((int)blockIdx.x >> 3) >= eighth) return;
   }
-  const int p0 = (((int)blockIdx.x & 7) * eighth + ((int)blockIdx.x >> 3)) * (CW * KE) + wave;
+  const int p0 = (((int)blockIdx.x & 7) * eighth + ((int)blockIdx.x >> 3)) * CW + wave;
   if (p0 >= E) return;  // no block-wide barriers below: waves are independent
-  if (REC && KE > 1) {
-    // several edges per wave: positions p0, p0 + CW, ...; the next record is requested under the current edge
-    const int bm = min(lane / 7, 8);
-    const uint32_t* r = rec_h + (size_t)p0 * cdv::CORR_REC_WORDS;
-    EdgeCoords ec;
-    ec.cval = 0;
-    ec.xb = __int_as_float((int)r[bm]);
-    ec.yb = __int_as_float((int)r[9 + bm]);
-    uint32_t w18 = r[18], w19 = r[19], w20 = r[20], w21 = r[21], w22 = r[22];
-    int p = p0;
-#pragma unroll 1
-    for (int k = 0; k < KE; k++) {
-      const int pn = p + CW;
-      const bool has_next = k + 1 < KE && pn < E;      // wave-uniform
-      ec.ixmin = (int)(short)(w21 & 0xffff); ec.ixmax = (int)w21 >> 16;
-      ec.iymin = (int)(short)(w22 & 0xffff); ec.iymax = (int)w22 >> 16;
-      NextRec nx;
-      int lane_it = lane;      // opaque per trip: what the edge derives from the lane index is recomputed, not kept across the loop
-      asm volatile("" : "+v"(lane_it));
-      corr_edge<CC, NLEV, SPLIT, true>(a, p, (int)w18, ec, w19, w20, w20 != 0xFFFFFFFFu, lane_it, raw, outT,
-                                       has_next ? rec_h + (size_t)pn * cdv::CORR_REC_WORDS : nullptr, &nx);
-      if (!has_next) break;
-      ec.xb = nx.xb; ec.yb = nx.yb;
-      w18 = __builtin_amdgcn_readfirstlane(nx.w18); w19 = __builtin_amdgcn_readfirstlane(nx.w19);
-      w20 = __builtin_amdgcn_readfirstlane(nx.w20); w21 = __builtin_amdgcn_readfirstlane(nx.w21);
-      w22 = __builtin_amdgcn_readfirstlane(nx.w22);
-      p = pn;
-    }
-    return;
-  }
   if (REC) {
     // ---- ONE round trip: record p0 of the packed input stream the index build wrote in processing order -- the 18
     // coordinates as one vector load, edge id and ring indices as scalar loads of the same line (no order[] -> coords /
@@ -874,7 +802,7 @@ __global__ __launch_bounds__(64 * CW) void corr_fused2_kernel(const uint32_t* __
     const int bx = (int)r[21], by = (int)r[22];   // extremes of floor(x), floor(y): (max << 16) | (min & 0xffff)
     ec.ixmin = (int)(short)(bx & 0xffff); ec.ixmax = bx >> 16;
     ec.iymin = (int)(short)(by & 0xffff); ec.iymax = by >> 16;
-    corr_edge<CC, NLEV, SPLIT, true>(a, p0, e, ec, kq, jq, jq != 0xFFFFFFFFu, lane, raw, outT);
+    corr_edge<CC, NLEV, true>(a, p0, e, ec, kq, jq, jq != 0xFFFFFFFFu, lane, raw, outT);
     return;
   }
   // ---- round trip 1: the 18 coordinates (one vector load) and the two indices (scalar loads) -----------------------
@@ -889,7 +817,7 @@ __global__ __launch_bounds__(64 * CW) void corr_fused2_kernel(const uint32_t* __
   const bool j_ok = ring_index(a.jj[e], a.jmod, a.jmagic, a.slots, jq);
   EdgeCoords ec;
   ec.cval = cval;
-  corr_edge<CC, NLEV, SPLIT, false>(a, p0, e, ec, kq, jq, k_ok && j_ok, lane, raw, outT);
+  corr_edge<CC, NLEV, false>(a, p0, e, ec, kq, jq, k_ok && j_ok, lane, raw, outT);
 }
 
 // ---- generic per-level kernel: planar layouts, any C / P / radius, f16 or f32 ----------------------
@@ -1382,7 +1310,7 @@ static int corr_fused_impl(const void* gmap, const void* fmap0_nhwc, const void*
                            const int64_t* kk, const int64_t* jj, const int32_t* order, void* out, int64_t E,
                            int64_t Ng, int64_t slots, int C, int H0, int W0, int H1, int W1, float scale0,
                            float scale1, int nlev, int64_t kmod, int64_t jmod, int gmap_pixel_major, void* stream,
-                           int out_stride, int out_off, int out_pitch, const float* coords_ref, float ref_mul, int split,
+                           int out_stride, int out_off, int out_pitch, const float* coords_ref, float ref_mul,
                            const uint32_t* rec = nullptr, const int32_t* dynE = nullptr) {
   CDV_REQUIRE(nlev == 1 || nlev == 2, CDV_ERR_ARG, "cdv_corr_fused: nlev must be 1 or 2");
   CDV_REQUIRE(C % 8 == 0 && C > 0 && C <= 128, CDV_ERR_UNSUPPORTED, "cdv_corr_fused: C must be a multiple of 8, <= 128");
@@ -1415,26 +1343,11 @@ static int corr_fused_impl(const void* gmap, const void* fmap0_nhwc, const void*
     const CorrArgs2 a{coords, kk, jj, order, (int)E, (uint32_t)kmod, (uint32_t)jmod, kmagic, jmagic, (uint32_t)Ng,
                       (uint32_t)slots, (const char*)gmap, (_Float16*)out, A0,
                       nlev == 2 ? level(fmap1_nhwc, H1, W1, scale1, ex1 - ex0) : A0, C, gmap_pixel_major, exp,
-                      out_stride, out_off, out_pitch, coords_ref, ref_mul, split, rec, dynE};
-    const int blocks = 8 * (int)cdv_div_up(E, 8 * CW * (rec ? EPW : 1));   // a multiple of 8: the kernel deals contiguous eighths to the XCDs
+                      out_stride, out_off, out_pitch, coords_ref, ref_mul, rec, dynE};
+    const int blocks = 8 * (int)cdv_div_up(E, 8 * CW);   // a multiple of 8: the kernel deals contiguous eighths to the XCDs
     const size_t smem2 = (size_t)CW * WAVE_LDS2_BYTES;
-    if (smem2 > 48 * 1024) {   // (experiment builds with more than 11 waves per workgroup)
-      static const hipError_t attr = [&] {
-        hipError_t e = hipSuccess, x;
-#define CDV_CATTR(...) if ((x = hipFuncSetAttribute((const void*)corr_fused2_kernel<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem2)) != hipSuccess) e = x;
-        CDV_CATTR(24, 2, false, true) CDV_CATTR(0, 2, false, true) CDV_CATTR(24, 2, true) CDV_CATTR(0, 2, true)
-        CDV_CATTR(24, 2) CDV_CATTR(0, 2) CDV_CATTR(24, 1) CDV_CATTR(0, 1)
-#undef CDV_CATTR
-        return e;
-      }();
-      CDV_HIP_CHECK(attr);
-    }
     if (rec) {   // packed input stream in processing order (cdv_corr_fused_stream)
-      CDV_REQUIRE(nlev == 2 && !split && coords_ref == nullptr, CDV_ERR_UNSUPPORTED, "cdv_corr_fused_stream: two fused levels only");
-      if (C == 24) hipLaunchKernelGGL((corr_fused2_kernel<24, 2, false, true>), dim3(blocks), dim3(64 * CW), smem2, s, rec, dynE, (int)E, blocks >> 3, a);
-      else hipLaunchKernelGGL((corr_fused2_kernel<0, 2, false, true>), dim3(blocks), dim3(64 * CW), smem2, s, rec, dynE, (int)E, blocks >> 3, a);
-    } else if (nlev == 2 && split) {   // levels kept apart (cdv_corr_fused_split): a variant of its own, so that the main kernel
-                              // keeps its 72 VGPRs (74 with the choice at run time: 6 instead of 7 waves per SIMD, +7 %)
+      CDV_REQUIRE(nlev == 2 && coords_ref == nullptr, CDV_ERR_UNSUPPORTED, "cdv_corr_fused_stream: two fused levels only");
       if (C == 24) hipLaunchKernelGGL((corr_fused2_kernel<24, 2, true>), dim3(blocks), dim3(64 * CW), smem2, s, rec, dynE, (int)E, blocks >> 3, a);
       else hipLaunchKernelGGL((corr_fused2_kernel<0, 2, true>), dim3(blocks), dim3(64 * CW), smem2, s, rec, dynE, (int)E, blocks >> 3, a);
     } else if (nlev == 2 && C == 24)
@@ -1446,8 +1359,8 @@ static int corr_fused_impl(const void* gmap, const void* fmap0_nhwc, const void*
     else
       hipLaunchKernelGGL((corr_fused2_kernel<0, 1>), dim3(blocks), dim3(64 * CW), smem2, s, rec, dynE, (int)E, blocks >> 3, a);
   } else {
-    CDV_REQUIRE(out_stride == 1 && out_off == 0 && coords_ref == nullptr && !split, CDV_ERR_UNSUPPORTED,
-                "cdv_corr_fused: split levels / checked calls need C <= 32");
+    CDV_REQUIRE(out_stride == 1 && out_off == 0 && coords_ref == nullptr, CDV_ERR_UNSUPPORTED,
+                "cdv_corr_fused: checked calls need C <= 32");
     LevelParams L0{(const _Float16*)fmap0_nhwc, H0, W0, 1.0f / scale0, 0};
     LevelParams L1{(const _Float16*)fmap1_nhwc, H1, W1, nlev == 2 ? 1.0f / scale1 : 1.0f, nlev == 2 ? ex1 - ex0 : 0};
     hipLaunchKernelGGL(corr_wide_kernel<4>, dim3(cdv_div_up(E, 4)), dim3(256), smem, s, (const _Float16*)gmap, L0, L1, coords,
@@ -1463,7 +1376,7 @@ extern "C" int cdv_corr_fused(const void* gmap, const void* fmap0_nhwc, const vo
                               int64_t Ng, int64_t slots, int C, int H0, int W0, int H1, int W1, float scale0,
                               float scale1, int nlev, int64_t kmod, int64_t jmod, int gmap_pixel_major, void* stream) {
   return corr_fused_impl(gmap, fmap0_nhwc, fmap1_nhwc, coords, kk, jj, order, out, E, Ng, slots, C, H0, W0, H1, W1, scale0,
-                         scale1, nlev, kmod, jmod, gmap_pixel_major, stream, 1, 0, 441, nullptr, 1.0f, 0);
+                         scale1, nlev, kmod, jmod, gmap_pixel_major, stream, 1, 0, 441, nullptr, 1.0f);
 }
 
 extern "C" int cdv_corr_fused_stream(const void* gmap, const void* fmap0_nhwc, const void* fmap1_nhwc, const void* records,
@@ -1472,7 +1385,7 @@ extern "C" int cdv_corr_fused_stream(const void* gmap, const void* fmap0_nhwc, c
   CDV_REQUIRE(records != nullptr, CDV_ERR_ARG, "cdv_corr_fused_stream: NULL record stream");
   CDV_REQUIRE(C <= 32, CDV_ERR_UNSUPPORTED, "cdv_corr_fused_stream: C must be <= 32");
   return corr_fused_impl(gmap, fmap0_nhwc, fmap1_nhwc, nullptr, nullptr, nullptr, nullptr, out, E, Ng, slots, C, H0, W0, H1,
-                         W1, scale0, scale1, 2, 0, 0, gmap_pixel_major, stream, 1, 0, 441, nullptr, 1.0f, 0,
+                         W1, scale0, scale1, 2, 0, 0, gmap_pixel_major, stream, 1, 0, 441, nullptr, 1.0f,
                          (const uint32_t*)records);
 }
 
@@ -1483,32 +1396,13 @@ extern "C" int cdv_corr_fused_stream_dyn(const void* gmap, const void* fmap0_nhw
   CDV_REQUIRE(records != nullptr && dyn != nullptr, CDV_ERR_ARG, "cdv_corr_fused_stream_dyn: NULL record stream / dynamic block");
   CDV_REQUIRE(C <= 32, CDV_ERR_UNSUPPORTED, "cdv_corr_fused_stream_dyn: C must be <= 32");
   return corr_fused_impl(gmap, fmap0_nhwc, fmap1_nhwc, nullptr, nullptr, nullptr, nullptr, out, E_bound, Ng, slots, C, H0, W0,
-                         H1, W1, scale0, scale1, 2, 0, 0, gmap_pixel_major, stream, 1, 0, 441, nullptr, 1.0f, 0,
+                         H1, W1, scale0, scale1, 2, 0, 0, gmap_pixel_major, stream, 1, 0, 441, nullptr, 1.0f,
                          (const uint32_t*)records, dyn + CDV_DYN_E);
 }
 
-extern "C" int cdv_corr_fused_split(const void* gmap, const void* fmap0_nhwc, const void* fmap1_nhwc, const float* coords,
-                                    const int64_t* kk, const int64_t* jj, const int32_t* order, void* out2, int64_t E,
-                                    int64_t Ng, int64_t slots, int C, int H0, int W0, int H1, int W1, float scale0,
-                                    float scale1, int64_t kmod, int64_t jmod, int gmap_pixel_major, void* stream) {
-  CDV_REQUIRE(C <= 32, CDV_ERR_UNSUPPORTED, "cdv_corr_fused_split: C must be <= 32");
-  return corr_fused_impl(gmap, fmap0_nhwc, fmap1_nhwc, coords, kk, jj, order, out2, E, Ng, slots, C, H0, W0, H1, W1, scale0,
-                         scale1, 2, kmod, jmod, gmap_pixel_major, stream, 1, 0, 884, nullptr, 1.0f, 1);
-}
-
-extern "C" int cdv_corr_level_checked(const void* gmap, const void* fmap_nhwc, const float* coords, const float* coords_ref,
-                                      float ref_mul, const int64_t* kk, const int64_t* jj, void* out2, int level, int64_t E,
-                                      int64_t Ng, int64_t slots, int C, int H, int W, float scale, int64_t kmod,
-                                      int64_t jmod, int gmap_pixel_major, void* stream) {
-  CDV_REQUIRE(level == 0 || level == 1, CDV_ERR_ARG, "cdv_corr_level_checked: level must be 0 or 1");
-  CDV_REQUIRE(coords_ref != nullptr && out2 != nullptr, CDV_ERR_ARG, "cdv_corr_level_checked: NULL argument");
-  CDV_REQUIRE(C <= 32, CDV_ERR_UNSUPPORTED, "cdv_corr_level_checked: C must be <= 32");
-  return corr_fused_impl(gmap, fmap_nhwc, nullptr, coords, kk, jj, nullptr, out2, E, Ng, slots, C, H, W, 0, 0, scale, 1.0f, 1,
-                         kmod, jmod, gmap_pixel_major, stream, 1, 442 * level, 884, coords_ref, ref_mul, 0);
-}
-
-// cdv_corr_level_checked into the INTERLEAVED two-level result of cdv_corr_fused ([E][441][2] halves: what SLAM.corr's
-// torch.stack(..., -1) produces): level `level` of element t of edge e lives at out[e * 882 + 2 t + level]
+// ONE level of the INTERLEAVED two-level result of cdv_corr_fused ([E][441][2] halves: what SLAM.corr's torch.stack(..., -1)
+// produces), level `level` of element t of edge e at out[e * 882 + 2 t + level]; an edge whose coordinates equal
+// coords_ref * ref_mul bit for bit is skipped (its values are in place already)
 extern "C" int cdv_corr_level_checked_interleaved(const void* gmap, const void* fmap_nhwc, const float* coords,
                                                   const float* coords_ref, float ref_mul, const int64_t* kk, const int64_t* jj,
                                                   void* out, int level, int64_t E, int64_t Ng, int64_t slots, int C, int H, int W,
@@ -1517,7 +1411,7 @@ extern "C" int cdv_corr_level_checked_interleaved(const void* gmap, const void* 
   CDV_REQUIRE(coords_ref != nullptr && out != nullptr, CDV_ERR_ARG, "cdv_corr_level_checked_interleaved: NULL argument");
   CDV_REQUIRE(C <= 32, CDV_ERR_UNSUPPORTED, "cdv_corr_level_checked_interleaved: C must be <= 32");
   return corr_fused_impl(gmap, fmap_nhwc, nullptr, coords, kk, jj, nullptr, out, E, Ng, slots, C, H, W, 0, 0, scale, 1.0f, 1,
-                         kmod, jmod, gmap_pixel_major, stream, 2, level, 882, coords_ref, ref_mul, 0);
+                         kmod, jmod, gmap_pixel_major, stream, 2, level, 882, coords_ref, ref_mul);
 }
 
 extern "C" int cdv_patchify_fwd(const void* net, const float* coords, void* patches, int B, int64_t M, int C, int H,

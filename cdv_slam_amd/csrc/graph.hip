@@ -846,7 +846,7 @@ extern "C" size_t cdv_graph_workspace_bytes(int64_t E_max, int64_t k_range) {
 
 extern "C" int cdv_graph_build(const int64_t* jj, const int64_t* kk, int64_t E, void* ws, size_t ws_bytes,
                                int64_t E_max, int64_t k_range, void* stream) {
-  return cdv_graph_build_neighbors(jj, kk, E, ws, ws_bytes, E_max, k_range, nullptr, nullptr, stream);
+  return cdv_graph_build_edges(nullptr, jj, kk, E, ws, ws_bytes, E_max, k_range, nullptr, nullptr, stream);
 }
 
 // Index build in two halves, so that cdv_update_prologue (prologue.hip) can run the histogram launch fused with the
@@ -855,7 +855,7 @@ extern "C" int cdv_graph_build(const int64_t* jj, const int64_t* kk, int64_t E, 
 int cdv_graph_prepare(const int64_t* jj, const int64_t* kk, int64_t E, void* ws, size_t ws_bytes, int64_t E_max,
                       int64_t k_range, int64_t* ix, int64_t* jx, void* stream, cdv::HistArgs* hist, int* hist_blocks) {
   (void)jj; (void)kk;
-  CDV_REQUIRE((ix == nullptr) == (jx == nullptr), CDV_ERR_ARG, "cdv_graph_build_neighbors: give both ix and jx or neither");
+  CDV_REQUIRE((ix == nullptr) == (jx == nullptr), CDV_ERR_ARG, "cdv_graph_build_edges: give both ix and jx or neither");
   CDV_REQUIRE(ws != nullptr, CDV_ERR_ARG, "cdv_graph_build: workspace is NULL");
   CDV_REQUIRE(E >= 0 && E < (int64_t)1 << 31, CDV_ERR_ARG, "cdv_graph_build: E out of range");
   CDV_REQUIRE(k_range >= 1 && E_max >= 1 && E <= E_max, CDV_ERR_ARG,
@@ -1033,11 +1033,6 @@ extern "C" int cdv_graph_build_edges(const int64_t* ii, const int64_t* jj, const
   if (rc != CDV_OK) return rc;
   if (hb > 0) hipLaunchKernelGGL(graph_hist_kernel, dim3(hb), dim3(256), 0, (hipStream_t)stream, h);
   return cdv_graph_finish(ii, jj, kk, E, ws, E_max, k_range, hb, ix, jx, stream);
-}
-
-extern "C" int cdv_graph_build_neighbors(const int64_t* jj, const int64_t* kk, int64_t E, void* ws, size_t ws_bytes,
-                                         int64_t E_max, int64_t k_range, int64_t* ix, int64_t* jx, void* stream) {
-  return cdv_graph_build_edges(nullptr, jj, kk, E, ws, ws_bytes, E_max, k_range, ix, jx, stream);
 }
 
 extern "C" const int32_t* cdv_graph_corr_order(const void* ws) {

@@ -110,7 +110,7 @@ extern "C" int cdv_update_prologue(
     // cdv_transform (P = 3, coords only)
     const float* poses, const float* patches, const float* intrinsics, const int64_t* ii, const int64_t* jj,
     const int64_t* kk, int64_t E, int tf_flags, float* coords,
-    // cdv_graph_build_neighbors
+    // cdv_graph_build_edges (ii = NULL)
     void* graph_ws, size_t graph_ws_bytes, int64_t E_max, int64_t k_range, int64_t* ix, int64_t* jx, void* stream) {
   CDV_REQUIRE(C % 8 == 0 && C > 0, CDV_ERR_ARG, "cdv_update_prologue: C must be a multiple of 8");
   CDV_REQUIRE(H % 4 == 0 && W % 4 == 0, CDV_ERR_ARG, "cdv_update_prologue: H and W must be multiples of 4");

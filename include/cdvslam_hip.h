@@ -187,25 +187,13 @@ int cdv_corr_fused(const void* gmap, const void* fmap0_nhwc, const void* fmap1_n
 
 /*
  * The reference's two-call sequence (slam.py:321-322: cuda_corr.forward on pyramid[0] with coords, then on pyramid[1] with
- * coords / 4, stacked by slam.py:323) served by one two-level launch and a check:
- *   cdv_corr_fused_split   = cdv_corr_fused with the levels kept apart: out2 [E][2][442] halves (each level a contiguous
- *                            run of 441, rows of 884 bytes), so that either level can be handed out as a tensor view;
- *   cdv_corr_level_checked = the SECOND call, given that the first already produced both levels into out2: every edge whose
- *                            coords equal coords_ref * ref_mul bit for bit keeps what is there, any other edge is
- *                            recomputed from coords into out2[e][level].  ~5 us when all match instead of a second
- *                            correlation.  C <= 32 only.
+ * coords / 4, stacked by slam.py:323) served by one two-level launch and a check.  cdv_corr_level_checked_interleaved is the
+ * SECOND call, given that the first (cdv_corr_fused) already produced both levels into out, the interleaved two-level
+ * result ([E][441][2] halves, exactly what SLAM.corr's torch.stack([corr1, corr2], -1) holds): every edge whose coords
+ * equal coords_ref * ref_mul bit for bit keeps what is there, any other edge is recomputed from coords into element t,
+ * level `level`, at out[e * 882 + 2 t + level].  ~5 us when all match instead of a second correlation.  Lets a drop-in hand
+ * out both per-level results as views of ONE buffer.  C <= 32 only.
  */
-int cdv_corr_fused_split(const void* gmap, const void* fmap0_nhwc, const void* fmap1_nhwc, const float* coords,
-                         const int64_t* kk, const int64_t* jj, const int32_t* order, void* out2, int64_t E, int64_t Ng,
-                         int64_t slots, int C, int H0, int W0, int H1, int W1, float scale0, float scale1, int64_t kmod,
-                         int64_t jmod, int gmap_pixel_major, void* stream);
-int cdv_corr_level_checked(const void* gmap, const void* fmap_nhwc, const float* coords, const float* coords_ref,
-                           float ref_mul, const int64_t* kk, const int64_t* jj, void* out2, int level, int64_t E,
-                           int64_t Ng, int64_t slots, int C, int H, int W, float scale, int64_t kmod, int64_t jmod,
-                           int gmap_pixel_major, void* stream);
-/* cdv_corr_level_checked writing into the interleaved two-level result of cdv_corr_fused ([E][441][2] halves, exactly what
- * SLAM.corr's torch.stack([corr1, corr2], -1) holds, slam.py:323): element t of edge e, level `level`, at
- * out[e * 882 + 2 t + level].  Lets a drop-in hand out both per-level results as views of ONE buffer. */
 int cdv_corr_level_checked_interleaved(const void* gmap, const void* fmap_nhwc, const float* coords, const float* coords_ref,
                                        float ref_mul, const int64_t* kk, const int64_t* jj, void* out, int level, int64_t E,
                                        int64_t Ng, int64_t slots, int C, int H, int W, float scale, int64_t kmod, int64_t jmod,
@@ -293,13 +281,10 @@ int cdv_graph_build(const int64_t* jj, const int64_t* kk, int64_t E, void* ws, s
 /* meta_host[8] <- {U, 0, kmin, kmax, jmin, jmax, error, E}; synchronises `stream`. */
 /* cdv_graph_build that also writes fastba.neighbors' result (ba.cpp:59-97) for the same (kk, jj) straight into
  * ix / jx [E] int64 -- the sweep that orders a patch's edges in time sees each edge's predecessor and successor
- * anyway, so the update path needs no separate neighbors launch.  ix == jx == NULL: same as cdv_graph_build. */
-int cdv_graph_build_neighbors(const int64_t* jj, const int64_t* kk, int64_t E, void* ws, size_t ws_bytes,
-                              int64_t E_max, int64_t k_range, int64_t* ix, int64_t* jx, void* stream);
-
-/* cdv_graph_build_neighbors given the source frames ii [E] as well (what cdv_update_prologue does): the per-patch edge
- * records then carry (edge id, ii, jj), so cdv_ba_forward walks them with one 16-byte load per edge instead of a dependent
- * chain of index loads.  ii == NULL: identical to cdv_graph_build_neighbors (the BA then reads ii itself). */
+ * anyway, so the update path needs no separate neighbors launch.  ix == jx == NULL: no neighbors.
+ * Given the source frames ii [E] as well (what cdv_update_prologue does), the per-patch edge records carry (edge id, ii,
+ * jj), so cdv_ba_forward walks them with one 16-byte load per edge instead of a dependent chain of index loads.
+ * ii == NULL: the BA reads ii itself. */
 int cdv_graph_build_edges(const int64_t* ii, const int64_t* jj, const int64_t* kk, int64_t E, void* ws, size_t ws_bytes,
                           int64_t E_max, int64_t k_range, int64_t* ix, int64_t* jx, void* stream);
 
@@ -314,7 +299,7 @@ int cdv_graph_read_meta_host(const void* ws, int64_t* meta_host, void* stream);
  * CDV_ERR_GRAPH_RANGE).
  * Launch 1 puts every edge's record {edge, ii, jj, kk} into its patch's slot in arrival order; launch 2 sorts each slot
  * into (jj, edge id) order -- the order std::stable_sort by jj gives on an ascending index list, ba.cpp:84-86 -- and writes
- * fastba.neighbors from it (ix / jx as in cdv_graph_build_neighbors, bit-exact), the correlation's processing order and,
+ * fastba.neighbors from it (ix / jx as in cdv_graph_build_edges, bit-exact), the correlation's processing order and,
  * when a coordinate source is bound (cdv_graph_bind_corr_stream), its packed input stream.  A patch with more than 32
  * edges keeps its first 32 records in the table and all of them in an overflow segment.
  * What it does NOT produce is torch::_unique's (kx, ku): no ranks exist (cdv_graph_get_unique refuses; cdv_graph_build* is
@@ -509,7 +494,7 @@ int cdv_update_prologue_table(const void* fmap_chw, void* fmap1_nhwc, void* fmap
 
 /*
  * cdv_frame_ingest + cdv_transform (P = 3, coordinates only) + the first launch of
- * cdv_graph_build_neighbors SIDE BY SIDE in one grid, then the rest of the index build.  The three have no mutual
+ * cdv_graph_build_edges SIDE BY SIDE in one grid, then the rest of the index build.  The three have no mutual
  * dependency at the start of SLAM.update (slam.py:480-526: ring writes :676-682, reproject :325-329, the edge
  * lists of this update) and each is a few microseconds of latency-bound work, so one launch costs the longest of
  * them instead of their sum.  Arguments as in the three functions (tf_flags: CDV_TF_LAYOUT_* / CDV_TF_TONLY);
