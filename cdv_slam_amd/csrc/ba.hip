@@ -917,6 +917,9 @@ static int ba_forward_impl(float* poses, float* patches, const float* intrinsics
   const bool big = N > BA_NMAX;   // global BA: panel-sparse Schur products + blocked multi-workgroup Cholesky
   CDV_REQUIRE(P == 3 || P == 1, CDV_ERR_UNSUPPORTED, "cdv_ba_forward: patch size P must be 3 or 1");
   CDV_REQUIRE(E >= 0 && E < ((int64_t)1 << 31), CDV_ERR_ARG, "cdv_ba_forward: E out of range");
+  CDV_REQUIRE_ALIGNED(target, 8, "cdv_ba_forward: target must be 8-byte aligned");      // a row is loaded as one float2
+  CDV_REQUIRE_ALIGNED(weight, 8, "cdv_ba_forward: weight must be 8-byte aligned");
+  CDV_REQUIRE_ALIGNED(ba_ws, 16, "cdv_ba_forward: ba_ws must be 16-byte aligned");
   if (E == 0 || iterations <= 0) return CDV_OK;
   GraphLayout GL;
   CDV_REQUIRE(cdv_graph_lookup(graph_ws, &GL), CDV_ERR_ARG, "cdv_ba_forward: graph_ws has no built graph");

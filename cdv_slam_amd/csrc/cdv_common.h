@@ -25,6 +25,10 @@
     }                                \
   } while (0)
 
+// a pointer a kernel accesses through a naturally aligned vector type: the alignment is part of the entry point's contract
+// (include/cdvslam_hip.h "Alignment"), checked before anything is enqueued.  NULL (an optional argument) passes.
+#define CDV_REQUIRE_ALIGNED(ptr, n, msg) CDV_REQUIRE((((uintptr_t)(ptr)) & (uintptr_t)((n) - 1)) == 0, CDV_ERR_ARG, msg)
+
 // after a kernel launch: catches launch-configuration errors without synchronising
 #define CDV_LAUNCH_CHECK() CDV_HIP_CHECK(hipGetLastError())
 

@@ -1194,6 +1194,7 @@ extern "C" int cdv_fmap_to_nhwc(const void* src_nchw, void* dst_nhwc, int64_t N,
                                 int64_t count, void* stream) {
   CDV_REQUIRE(C % 8 == 0 && C > 0, CDV_ERR_ARG, "cdv_fmap_to_nhwc: C must be a multiple of 8");
   CDV_REQUIRE(first >= 0 && count >= 0 && first + count <= N, CDV_ERR_ARG, "cdv_fmap_to_nhwc: slot range");
+  CDV_REQUIRE_ALIGNED(dst_nhwc, 16, "cdv_fmap_to_nhwc: dst_nhwc must be 16-byte aligned");
   if (count == 0) return CDV_OK;
   const int64_t total = count * H * W * (C / 8);
   const int blocks = cdv_div_up(total, 256) < 16384 ? cdv_div_up(total, 256) : 16384;
@@ -1211,6 +1212,9 @@ extern "C" int cdv_fmap_sync_nhwc(const void* src_nchw, void* dst_nhwc, int64_t 
                                   int parity, void* stream) {
   CDV_REQUIRE(C % 8 == 0 && C > 0, CDV_ERR_ARG, "cdv_fmap_sync_nhwc: C must be a multiple of 8");
   CDV_REQUIRE(src_nchw && dst_nhwc && ws && N >= 0 && H > 0 && W > 0, CDV_ERR_ARG, "cdv_fmap_sync_nhwc: bad argument");
+  CDV_REQUIRE_ALIGNED(dst_nhwc, 16, "cdv_fmap_sync_nhwc: dst_nhwc must be 16-byte aligned");
+  CDV_REQUIRE_ALIGNED(src_nchw, 4, "cdv_fmap_sync_nhwc: src_nchw must be 4-byte aligned");
+  CDV_REQUIRE_ALIGNED(ws, 16, "cdv_fmap_sync_nhwc: ws must be 16-byte aligned");
   if (N == 0) return CDV_OK;
   uint64_t* fp = (uint64_t*)ws;
   uint64_t* fp_new = fp + (size_t)(parity & 1) * N * FP_PARTS;
@@ -1232,6 +1236,12 @@ extern "C" int cdv_shadows_sync(const cdv_shadow_ring* rings, int n_rings, const
   CDV_REQUIRE(n_rings >= 0 && n_rings <= 2 && (n_rings == 0 || rings != nullptr), CDV_ERR_ARG, "cdv_shadows_sync: 0 to 2 rings");
   const bool do_g = gmap_planar != nullptr && gmap_pm != nullptr && Ng > 0;
   CDV_REQUIRE(!do_g || (C_tiles % 8 == 0 && C_tiles > 0), CDV_ERR_ARG, "cdv_shadows_sync: C of the tiles must be a multiple of 8");
+  CDV_REQUIRE_ALIGNED(gmap_pm, 16, "cdv_shadows_sync: gmap_pm must be 16-byte aligned");
+  for (int q = 0; q < n_rings; q++) {
+    CDV_REQUIRE_ALIGNED(rings[q].dst_nhwc, 16, "cdv_shadows_sync: dst_nhwc must be 16-byte aligned");
+    CDV_REQUIRE_ALIGNED(rings[q].src_nchw, 4, "cdv_shadows_sync: src_nchw must be 4-byte aligned");
+    CDV_REQUIRE_ALIGNED(rings[q].ws, 16, "cdv_shadows_sync: ws must be 16-byte aligned");
+  }
   ShadowJobs J;
   J.n = 0;
   int fp_total = 0, cv_total = 0;
@@ -1274,6 +1284,9 @@ extern "C" int cdv_frame_ingest(const void* fmap_chw, void* fmap1_nhwc, void* fm
   CDV_REQUIRE(C % 8 == 0 && C > 0, CDV_ERR_ARG, "cdv_fmap_ingest: C must be a multiple of 8");
   CDV_REQUIRE(H % 4 == 0 && W % 4 == 0, CDV_ERR_ARG, "cdv_fmap_ingest: H and W must be multiples of 4");
   CDV_REQUIRE(slot >= 0, CDV_ERR_ARG, "cdv_fmap_ingest: slot");
+  CDV_REQUIRE_ALIGNED(fmap1_nhwc, 16, "cdv_fmap_ingest: fmap1_nhwc must be 16-byte aligned");
+  CDV_REQUIRE_ALIGNED(fmap2_nhwc, 16, "cdv_fmap_ingest: fmap2_nhwc must be 16-byte aligned");
+  CDV_REQUIRE_ALIGNED(gmap_pm, 16, "cdv_frame_ingest: gmap_pm must be 16-byte aligned");
   const bool do_g = gmap_planar != nullptr && gmap_pm != nullptr && gmap_count > 0;
   CDV_REQUIRE(!do_g || (gmap_first >= 0 && gmap_first + gmap_count <= Ng), CDV_ERR_ARG, "cdv_frame_ingest: tile range");
   const int64_t total = (int64_t)(H / 4) * (W / 4) * (C / 8) * 16;   // one thread per pixel and 8-channel group
@@ -1297,6 +1310,7 @@ extern "C" int cdv_gmap_to_pixel_major(const void* gmap_planar, void* gmap_pm, i
                                        int64_t count, void* stream) {
   CDV_REQUIRE(C % 8 == 0 && C > 0, CDV_ERR_ARG, "cdv_gmap_to_pixel_major: C must be a multiple of 8");
   CDV_REQUIRE(first >= 0 && count >= 0 && first + count <= Ng, CDV_ERR_ARG, "cdv_gmap_to_pixel_major: tile range");
+  CDV_REQUIRE_ALIGNED(gmap_pm, 16, "cdv_gmap_to_pixel_major: gmap_pm must be 16-byte aligned");
   if (count == 0) return CDV_OK;
   const int64_t total = count * 9 * (C / 8);
   const int blocks = cdv_div_up(total, 256) < 16384 ? cdv_div_up(total, 256) : 16384;
@@ -1319,6 +1333,10 @@ static int corr_fused_impl(const void* gmap, const void* fmap0_nhwc, const void*
   CDV_REQUIRE(scale0 > 0.f && frexpf(scale0, &ex0) == 0.5f && (nlev == 1 || (scale1 > 0.f && frexpf(scale1, &ex1) == 0.5f)),
               CDV_ERR_UNSUPPORTED, "cdv_corr_fused: pyramid scales must be powers of two (1 and 4 in SLAM.corr)");
   CDV_REQUIRE(fmap0_nhwc != nullptr && (nlev == 1 || fmap1_nhwc != nullptr), CDV_ERR_ARG, "cdv_corr_fused: NULL map");
+  CDV_REQUIRE_ALIGNED(fmap0_nhwc, 16, "cdv_corr_fused: fmap0_nhwc must be 16-byte aligned");
+  CDV_REQUIRE_ALIGNED(nlev == 2 ? fmap1_nhwc : nullptr, 16, "cdv_corr_fused: fmap1_nhwc must be 16-byte aligned");
+  CDV_REQUIRE_ALIGNED(gmap_pixel_major ? gmap : nullptr, 16, "cdv_corr_fused: pixel-major gmap must be 16-byte aligned");
+  CDV_REQUIRE_ALIGNED(out, 4, "cdv_corr_fused: out must be 4-byte aligned");
   CDV_REQUIRE(cdv_fmap_padded_elems(slots, C, H0, W0) * 2 < ((size_t)1 << 32) &&
                   (nlev == 1 || cdv_fmap_padded_elems(slots, C, H1, W1) * 2 < ((size_t)1 << 32)),
               CDV_ERR_UNSUPPORTED, "cdv_corr_fused: a feature ring of 4 GB or more");

@@ -218,6 +218,8 @@ extern "C" int cdv_edges_remove(const uint8_t* remove, int64_t E, void* ws, cons
                                 float* target_r, float* weight_r, int64_t r0, int32_t* counts_host, void* stream) {
   CDV_REQUIRE(E >= 0 && E < ((int64_t)1 << 31), CDV_ERR_ARG, "cdv_edges_remove: E out of range");
   CDV_REQUIRE(net == nullptr || net_bytes % 4 == 0, CDV_ERR_ARG, "cdv_edges_remove: net row size must be a multiple of 4");
+  CDV_REQUIRE_ALIGNED(net, 4, "cdv_edges_remove: net must be 4-byte aligned");
+  CDV_REQUIRE_ALIGNED(net_out, 4, "cdv_edges_remove: net_out must be 4-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   int32_t* meta = (int32_t*)ws;          // [16]: kept, removed, arrival counter
   int32_t* counts = meta + 16;

@@ -826,6 +826,7 @@ void cdv_graph_forget(const void* ws) {
 // A bound correlation stream is dropped.
 extern "C" int cdv_graph_workspace_init(void* ws, size_t ws_bytes, int64_t E_max, int64_t k_range, void* stream) {
   CDV_REQUIRE(ws != nullptr, CDV_ERR_ARG, "cdv_graph_workspace_init: workspace is NULL");
+  CDV_REQUIRE_ALIGNED(ws, 16, "cdv_graph_workspace_init: workspace must be 16-byte aligned");
   CDV_REQUIRE(k_range >= 1 && k_range < ((int64_t)1 << 31) - 64 && E_max >= 1, CDV_ERR_ARG, "cdv_graph_workspace_init: bad sizes");
   const GraphLayout L = graph_layout(E_max, k_range);
   CDV_REQUIRE(L.total <= ws_bytes, CDV_ERR_WORKSPACE, "cdv_graph_workspace_init: workspace too small for (E_max, k_range)");
@@ -857,6 +858,7 @@ int cdv_graph_prepare(const int64_t* jj, const int64_t* kk, int64_t E, void* ws,
   (void)jj; (void)kk;
   CDV_REQUIRE((ix == nullptr) == (jx == nullptr), CDV_ERR_ARG, "cdv_graph_build_edges: give both ix and jx or neither");
   CDV_REQUIRE(ws != nullptr, CDV_ERR_ARG, "cdv_graph_build: workspace is NULL");
+  CDV_REQUIRE_ALIGNED(ws, 16, "cdv_graph_build: workspace must be 16-byte aligned");
   CDV_REQUIRE(E >= 0 && E < (int64_t)1 << 31, CDV_ERR_ARG, "cdv_graph_build: E out of range");
   CDV_REQUIRE(k_range >= 1 && E_max >= 1 && E <= E_max, CDV_ERR_ARG,
               "cdv_graph_build: need 1 <= E <= E_max, k_range >= 1");
@@ -945,6 +947,7 @@ int cdv_graph_table_prepare(const int64_t* ii, const int64_t* jj, const int64_t*
                             cdv::TFillArgs* fill, int* fill_blocks, const int32_t* dyn) {
   CDV_REQUIRE((ix == nullptr) == (jx == nullptr), CDV_ERR_ARG, "cdv_graph_build_table: give both ix and jx or neither");
   CDV_REQUIRE(ws != nullptr, CDV_ERR_ARG, "cdv_graph_build_table: workspace is NULL");
+  CDV_REQUIRE_ALIGNED(ws, 16, "cdv_graph_build_table: workspace must be 16-byte aligned");
   CDV_REQUIRE(E >= 0 && E < (int64_t)1 << 31, CDV_ERR_ARG, "cdv_graph_build_table: E out of range");
   CDV_REQUIRE(k_range >= 1 && k_range < ((int64_t)1 << 31) - 64 && E_max >= 1 && E <= E_max, CDV_ERR_ARG,
               "cdv_graph_build_table: need 1 <= E <= E_max, 1 <= k_range < 2^31");
@@ -1045,6 +1048,7 @@ extern "C" int cdv_graph_bind_corr_stream(void* ws, const float* coords, int64_t
                                           int64_t slots, float scale0) {
   CDV_REQUIRE(scale0 > 0.f, CDV_ERR_ARG, "cdv_graph_bind_corr_stream: scale of level 0 must be positive");
   CDV_REQUIRE(ws != nullptr, CDV_ERR_ARG, "cdv_graph_bind_corr_stream: workspace is NULL");
+  CDV_REQUIRE_ALIGNED(coords, 8, "cdv_graph_bind_corr_stream: coords must be 8-byte aligned");      // the builds read float2 pairs
   CDV_REQUIRE(kmod >= 0 && jmod >= 0 && kmod < ((int64_t)1 << 31) && jmod < ((int64_t)1 << 31) && Ng >= 0 &&
                   Ng < ((int64_t)1 << 31) && slots >= 0 && slots < ((int64_t)1 << 31),
               CDV_ERR_ARG, "cdv_graph_bind_corr_stream: moduli / ring sizes out of range");

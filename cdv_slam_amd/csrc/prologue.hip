@@ -57,6 +57,11 @@ static int prologue_table_impl(
   CDV_REQUIRE(fmap_chw && fmap1_nhwc && fmap2_nhwc && coords && poses && patches && intrinsics && ii, CDV_ERR_ARG,
               "cdv_update_prologue_table: NULL buffer");
   CDV_REQUIRE(((uintptr_t)coords & 15) == 0, CDV_ERR_ARG, "cdv_update_prologue_table: coords must be 16-byte aligned");
+  // the per-edge pass loads an intrinsics row as one 16-byte word (graph.hip)
+  CDV_REQUIRE(((uintptr_t)intrinsics & 15) == 0, CDV_ERR_ARG, "cdv_update_prologue_table: intrinsics must be 16-byte aligned");
+  CDV_REQUIRE_ALIGNED(fmap1_nhwc, 16, "cdv_update_prologue_table: fmap1_nhwc must be 16-byte aligned");
+  CDV_REQUIRE_ALIGNED(fmap2_nhwc, 16, "cdv_update_prologue_table: fmap2_nhwc must be 16-byte aligned");
+  CDV_REQUIRE_ALIGNED(gmap_pm, 16, "cdv_update_prologue_table: gmap_pm must be 16-byte aligned");
   const bool do_g = gmap_planar != nullptr && gmap_pm != nullptr && gmap_count > 0;
   CDV_REQUIRE(!do_g || (gmap_first >= 0 && gmap_first + gmap_count <= Ng), CDV_ERR_ARG, "cdv_update_prologue_table: tile range");
   cdv::TFillArgs fill;
@@ -116,6 +121,9 @@ extern "C" int cdv_update_prologue(
   CDV_REQUIRE(H % 4 == 0 && W % 4 == 0, CDV_ERR_ARG, "cdv_update_prologue: H and W must be multiples of 4");
   CDV_REQUIRE(slot >= 0, CDV_ERR_ARG, "cdv_update_prologue: slot");
   CDV_REQUIRE(fmap_chw && fmap1_nhwc && fmap2_nhwc && coords, CDV_ERR_ARG, "cdv_update_prologue: NULL buffer");
+  CDV_REQUIRE_ALIGNED(fmap1_nhwc, 16, "cdv_update_prologue: fmap1_nhwc must be 16-byte aligned");
+  CDV_REQUIRE_ALIGNED(fmap2_nhwc, 16, "cdv_update_prologue: fmap2_nhwc must be 16-byte aligned");
+  CDV_REQUIRE_ALIGNED(gmap_pm, 16, "cdv_update_prologue: gmap_pm must be 16-byte aligned");
   const bool do_g = gmap_planar != nullptr && gmap_pm != nullptr && gmap_count > 0;
   CDV_REQUIRE(!do_g || (gmap_first >= 0 && gmap_first + gmap_count <= Ng), CDV_ERR_ARG, "cdv_update_prologue: tile range");
   cdv::HistArgs hist;

@@ -281,7 +281,9 @@ extern "C" int cdv_transform(const float* poses, const float* patches, const flo
   const int threads = 64;  // E ~ 5e4: small blocks spread the edges over all 256 CUs
   const int blocks = cdv_div_up(E, threads);
   const cdv::TfArgs A{poses, patches, intrinsics, ii, jj, kk, E, flags, coords, validpx, valid, Ji, Jj, Jz};
-  if (P == 3 && !validpx && !Ji && ((uintptr_t)coords & 15) == 0)
+  // the wave-wide kernel stores coords and loads an intrinsics row 16 bytes at a time: a caller's view that is not 16-byte
+  // aligned goes to the lane-per-edge kernel (same values), the header promises no alignment here
+  if (P == 3 && !validpx && !Ji && (((uintptr_t)coords | (uintptr_t)intrinsics) & 15) == 0)
     hipLaunchKernelGGL(transform_coords3_kernel, dim3(blocks), dim3(64), 0, s, A);
   else if (P == 3)
     hipLaunchKernelGGL(transform_kernel<3>, dim3(blocks), dim3(threads), 0, s, A);

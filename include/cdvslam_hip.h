@@ -27,6 +27,25 @@
  *     Never calls exit() (the reference does, block_e.cu:20-27, ba.cpp:151-152).
  *   - index tensors are int64 (torch.long) exactly as the reference passes them.
  *   - float layouts are the reference's contiguous torch layouts unless stated otherwise.
+ *   - Alignment.  Every pointer must have the alignment of its element type (2 bytes for f16, 4 for f32 / int32, 8 for int64).
+ *     The pointers below are accessed through wider vector types and need MORE; an entry point that is handed one of them
+ *     with less returns CDV_ERR_ARG before it enqueues anything.  A fresh torch allocation (256 bytes) satisfies all of them;
+ *     a view at an odd element offset may not.
+ *       16 bytes  the padded channels-last rings, wherever they are read or written (dst_nhwc, fmap1_nhwc, fmap2_nhwc,
+ *                 fmap0_nhwc: cdv_fmap_to_nhwc, cdv_fmap_sync_nhwc, cdv_shadows_sync, cdv_fmap_ingest, cdv_frame_ingest, the
+ *                 prologues, cdv_corr_fused*, cdv_corr_level_checked_interleaved);
+ *                 the pixel-major tile array gmap_pm, written (cdv_gmap_to_pixel_major, cdv_frame_ingest, cdv_shadows_sync, the
+ *                 prologues) or read (gmap of the correlation entry points when gmap_pixel_major != 0);
+ *                 coords and intrinsics of cdv_update_prologue_table / _dyn;
+ *                 every workspace (graph_ws, ba_ws, the ws of cdv_fmap_sync_nhwc / cdv_shadows_sync)
+ *        8 bytes  target and weight of cdv_ba_forward / _dyn (a row is one load); coords of cdv_graph_bind_corr_stream
+ *        4 bytes  out of the correlation entry points (f16 rows written as 32-bit words); src_nchw of cdv_fmap_sync_nhwc /
+ *                 cdv_shadows_sync (fingerprinted as 32-bit words); net / net_out of cdv_edges_remove; the buffers of
+ *                 cdv_frames_keyframe_shift (which picks 16- or 4-byte pieces by what the base allows)
+ *     Everything else -- in particular every pointer of cdv_transform (a coords or intrinsics pointer that is not 16-byte
+ *     aligned selects the lane-per-edge kernel, same values), cdv_fastba_reproject, cdv_flow_mag, cdv_point_cloud, cdv_lie_op,
+ *     cdv_corr_fwd, the patchify calls, the planar tile array and the index lists -- needs its element's alignment only: wide
+ *     accesses to those go through types declared 4-byte aligned, which global memory takes.
  */
 #ifndef CDVSLAM_HIP_H
 #define CDVSLAM_HIP_H
@@ -483,8 +502,8 @@ int cdv_point_cloud(const float* poses, const float* patches, const float* intri
  * pass, launch 2 = slot sort + neighbors next to the per-edge work -- the reprojection (coords [1,E,2,3,3], the layout
  * SLAM.reproject returns, slam.py:325-329), the correlation's processing order and its packed input stream (ring sizes as
  * bound with cdv_graph_bind_corr_stream; its coords argument is not used here: the coordinates go from registers into
- * both places).  Two launches for everything in front of the correlation (the ranked variant: four).  coords 16-byte
- * aligned; P = 3. */
+ * both places).  Two launches for everything in front of the correlation (the ranked variant: four).  coords and intrinsics
+ * 16-byte aligned (see "Alignment" at the top); P = 3. */
 int cdv_update_prologue_table(const void* fmap_chw, void* fmap1_nhwc, void* fmap2_nhwc, int slot, int C, int H, int W,
                               const void* gmap_planar, void* gmap_pm, int64_t Ng, int64_t gmap_first, int64_t gmap_count,
                               const float* poses, const float* patches, const float* intrinsics, const int64_t* ii,
