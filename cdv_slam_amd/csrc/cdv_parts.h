@@ -1,6 +1,6 @@
 // cdv_parts.h -- bodies of the three independent per-frame kernels that open an update (feature / tile ingest,
 // reprojection, patch-id histogram), as device functions taking an explicit (block, number of blocks): each is
-// launched on its own behind its C entry point (corr.hip, reproject.hip, graph.hip) and all three side by side in
+// launched on its own behind its C entry point (rings.hip, reproject.hip, graph.hip) and all three side by side in
 // ONE launch by cdv_update_prologue (prologue.hip) -- they are latency-bound (a few microseconds of work each), so
 // sharing a launch costs the longest of them instead of their sum.
 #pragma once
@@ -10,7 +10,7 @@
 
 namespace cdv {
 
-// ---- padded channels-last feature rings (corr.hip) --------------------------------------------------------
+// ---- padded channels-last feature rings (written by rings.hip, gathered from by corr.hip) ---------------------
 constexpr int PART_PADX = CDV_FMAP_PADX, PART_PADY = CDV_FMAP_PADY;
 
 struct IngestArgs {

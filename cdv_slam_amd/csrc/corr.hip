@@ -18,6 +18,7 @@
 //   * the [882]-half row of the edge is staged in LDS (over the raw volume) and leaves as 16-byte-per-lane stores.
 // corr_fused2_kernel is the product kernel (C <= 32: CDV-SLAM's DIMF = 24); corr_wide_kernel serves C up to 128 (DPVO).
 // Algorithmic HBM bytes per edge: 1764 out + 72 coords + 16 idx (+ the feature maps once): DESIGN.md.
+// (The rings and tiles it reads are kept by rings.hip; the reference-shaped per-level operators are altcorr_fwd.hip.)
 #include <math.h>
 #include <stdlib.h>
 
@@ -36,7 +37,7 @@ CDV_STAMP_TU(corr)
 
 namespace {
 
-// HBM layout of the feature rings the fused kernel gathers from ("padded channels-last"):
+// HBM layout of the feature rings the fused kernel gathers from ("padded channels-last"; written by rings.hip):
 //   [slot][H + 2*PADY][W + 2*PADX][C] f16, zero margins.  A 16 x 12 window box whose origin is clamped to
 //   [-PADX, W] x [-PADY, H] never leaves the allocation, and everything it reads outside the image is the
 //   zero the reference's out-of-bounds rule asks for (correlation_kernel.cu:122) -- no per-lane bounds
@@ -820,581 +821,98 @@ __global__ __launch_bounds__(64 * CW) void corr_fused2_kernel(const uint32_t* __
   corr_edge<CC, NLEV, false>(a, p0, e, ec, kq, jq, k_ok && j_ok, lane, raw, outT);
 }
 
-// ---- generic per-level kernel: planar layouts, any C / P / radius, f16 or f32 ----------------------
-template <typename T>
-__global__ __launch_bounds__(256) void corr_generic_kernel(const T* __restrict__ fmap1, const T* __restrict__ fmap2,
-                                                           const float* __restrict__ coords,
-                                                           const int64_t* __restrict__ us,
-                                                           const int64_t* __restrict__ vs, T* __restrict__ out,
-                                                           int64_t M, int64_t N1, int64_t N2, int C, int P, int H2,
-                                                           int W2, int R) {
-  const int D1 = 2 * R + 1;
-  const int64_t total = M * D1 * D1 * P * P;
-  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
-       idx += (int64_t)gridDim.x * blockDim.x) {
-    int64_t t = idx;
-    const int j0 = (int)(t % P); t /= P;
-    const int i0 = (int)(t % P); t /= P;
-    const int yo = (int)(t % D1); t /= D1;
-    const int xo = (int)(t % D1); t /= D1;
-    const int64_t m = t;
-    const int64_t ix = us[m], jx = vs[m];
-    const float x = coords[((m * 2 + 0) * P + i0) * P + j0];
-    const float y = coords[((m * 2 + 1) * P + i0) * P + j0];
-    const float fxf = floorf(x), fyf = floorf(y);
-    const float dx = (float)(T)(x - fxf), dy = (float)(T)(y - fyf);
-    const int fx = (int)fminf(fmaxf(fxf, -1.0e6f), 1.0e6f), fy = (int)fminf(fmaxf(fyf, -1.0e6f), 1.0e6f);
-    float c[2][2];
-    const bool idx_ok = ix >= 0 && ix < N1 && jx >= 0 && jx < N2;
-#pragma unroll
-    for (int a = 0; a < 2; a++)
-#pragma unroll
-      for (int b = 0; b < 2; b++) {
-        const int i1 = fy + yo + a - R, j1 = fx + xo + b - R;
-        float s = 0.f;
-        if (idx_ok && i1 >= 0 && i1 < H2 && j1 >= 0 && j1 < W2) {
-          const T* p1 = fmap1 + ((ix * C) * P + i0) * P + j0;
-          const T* p2 = fmap2 + ((jx * C) * (int64_t)H2 + i1) * W2 + j1;
-          for (int ch = 0; ch < C; ch++) s += (float)p1[(int64_t)ch * P * P] * (float)p2[(int64_t)ch * H2 * W2];
-        }
-        c[a][b] = s;
-      }
-    const float v = (1.f - dx) * (1.f - dy) * c[0][0] + dx * (1.f - dy) * c[0][1] + (1.f - dx) * dy * c[1][0] +
-                    dx * dy * c[1][1];
-    out[idx] = (T)v;
-  }
-}
-
-// ---- layout kernels -----------------------------------------------------------------------------------
-// planar [N][C][H][W] -> padded channels-last [N][H+2PADY][W+2PADX][C] (interior only; the margins are
-// zeroed once at allocation); one thread per (pixel, 8-channel group): 8 strided 2-byte reads (coalesced
-// across the wave along W), one 16-byte write.
-__global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const _Float16* __restrict__ src,
-                                                           _Float16* __restrict__ dst, int64_t first, int64_t count,
-                                                           int C, int H, int W) {
-  const int G = C / 8;
-  const int64_t total = count * H * W * G;
-  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
-       idx += (int64_t)gridDim.x * blockDim.x) {
-    // x fastest so that the planar reads of a wave are contiguous
-    int64_t t = idx;
-    const int xw = (int)(t % W); t /= W;
-    const int gq = (int)(t % G); t /= G;
-    const int yh = (int)(t % H); t /= H;
-    const int64_t nslot = first + t;
-    cdv_half8 v;
-#pragma unroll
-    for (int j = 0; j < 8; j++) v[j] = src[((nslot * C + 8 * gq + j) * H + yh) * W + xw];
-    *reinterpret_cast<cdv_half8*>(dst + ((nslot * (H + 2 * PADY) + yh + PADY) * (W + 2 * PADX) + xw + PADX) * C +
-                                  8 * gq) = v;
-  }
-}
-
-// ---- a planar ring whose writer is somebody else (the reference's slam.py writes fmap1_[:, n % mem] with torch ops) kept
-// in step with its channels-last shadow WITHOUT converting all of it every frame: pass 1 fingerprints every slot of the
-// planar ring (a read of the ring: 21 MB at level 0), pass 2 converts only the slots whose fingerprint differs from
-// the one taken at the previous sync (normally ONE).  Fingerprint = FP_PARTS position-keyed 64-bit sums per slot.
-constexpr int FP_PARTS = 16;      // workgroups (and partial sums) per slot
-
-__device__ __forceinline__ void fingerprint_body(const uint32_t* __restrict__ src, int64_t words_per_slot,
-                                                 uint64_t* __restrict__ fp, int bid) {
-  const int slot = bid / FP_PARTS, part = bid % FP_PARTS;
-  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-  const u32x4* p = reinterpret_cast<const u32x4*>(src + (size_t)slot * words_per_slot);
-  const int64_t n4 = words_per_slot / 4;        // slots are multiples of 16 bytes (C % 8 == 0)
-  uint64_t acc = 0;
-  for (int64_t i = (int64_t)part * 256 + threadIdx.x; i < n4; i += (int64_t)FP_PARTS * 256) {
-    const u32x4 v = p[i];
-    const uint64_t key = 0x9E3779B97F4A7C15ull + 2ull * (uint64_t)i;           // odd, different for every position
-    acc += ((uint64_t)v[0] | ((uint64_t)v[1] << 32)) * key;
-    acc += ((uint64_t)v[2] | ((uint64_t)v[3] << 32)) * (key ^ 0xD6E8FEB86659FD92ull);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
-  __shared__ uint64_t sw[4];
-  if ((threadIdx.x & 63) == 0) sw[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) fp[(size_t)slot * FP_PARTS + part] = (sw[0] + sw[1]) + (sw[2] + sw[3]) + 1ull;   // never 0 = "no fingerprint yet"
-}
-
-__global__ __launch_bounds__(256) void fmap_fingerprint_kernel(const uint32_t* __restrict__ src, int64_t words_per_slot,
-                                                               uint64_t* __restrict__ fp) {
-  fingerprint_body(src, words_per_slot, fp, (int)blockIdx.x);
-}
-
-__device__ __forceinline__ void dirty_body(const _Float16* __restrict__ src, _Float16* __restrict__ dst, int C, int H, int W,
-                                           const uint64_t* __restrict__ fp_new, const uint64_t* __restrict__ fp_old,
-                                           int wg_per_slot, int32_t* __restrict__ n_dirty, int bid) {
-  const int64_t nslot = bid / wg_per_slot;
-  const int wg = bid % wg_per_slot;
-  bool same = true;
-#pragma unroll
-  for (int i = 0; i < FP_PARTS; i++) same = same && fp_new[nslot * FP_PARTS + i] == fp_old[nslot * FP_PARTS + i];
-  if (same) return;                                  // workgroup-uniform
-  if (wg == 0 && threadIdx.x == 0 && n_dirty) atomicAdd(n_dirty, 1);
-  const int G = C / 8;
-  const int64_t total = (int64_t)H * W * G;
-  for (int64_t idx = (int64_t)wg * 256 + threadIdx.x; idx < total; idx += (int64_t)wg_per_slot * 256) {
-    int64_t t = idx;
-    const int xw = (int)(t % W); t /= W;
-    const int gq = (int)(t % G); t /= G;
-    const int yh = (int)t;
-    cdv_half8 v;
-#pragma unroll
-    for (int j = 0; j < 8; j++) v[j] = src[((nslot * C + 8 * gq + j) * H + yh) * W + xw];
-    *reinterpret_cast<cdv_half8*>(dst + ((nslot * (H + 2 * PADY) + yh + PADY) * (W + 2 * PADX) + xw + PADX) * C +
-                                  8 * gq) = v;
-  }
-}
-
-__global__ __launch_bounds__(256) void nchw_to_nhwc_dirty_kernel(const _Float16* __restrict__ src,
-                                                                 _Float16* __restrict__ dst, int C, int H, int W,
-                                                                 const uint64_t* __restrict__ fp_new,
-                                                                 const uint64_t* __restrict__ fp_old, int wg_per_slot,
-                                                                 int32_t* __restrict__ n_dirty) {
-  dirty_body(src, dst, C, H, W, fp_new, fp_old, wg_per_slot, n_dirty, (int)blockIdx.x);
-}
-
-// ---- the same two passes for SEVERAL rings at once, the tiles' conversion riding the second (cdv_shadows_sync): what an
-// unchanged slam.py needs in front of its correlation -- both pyramid levels' shadows and the tile shadow in step -- is five
-// launches through the single-ring entry points and two here.  Same bodies, same bytes.
-struct ShadowJob {
-  const _Float16* src; _Float16* dst;
-  uint64_t *fp_new; const uint64_t* fp_old;
-  int32_t* n_dirty;
-  int64_t words_per_slot;
-  int C, H, W, wg_per_slot, fp_blocks, cv_blocks;
-};
-struct ShadowJobs {
-  ShadowJob j[2];
-  int n;
-  const _Float16* g_src; _Float16* g_dst;     // tiles (NULL: none)
-  int64_t g_count;
-  int g_C, g_blocks;
+// Host-side arguments of one fused launch.  What an entry point does not set keeps the value of the plain two-level call
+// over coords / kk / jj: a dense [E][882] result, no reference coordinates, no record stream, edge count on the host.
+struct FusedCall {
+  const void *gmap = nullptr, *fmap0_nhwc = nullptr, *fmap1_nhwc = nullptr;
+  const float *coords = nullptr, *coords_ref = nullptr;
+  const int64_t *kk = nullptr, *jj = nullptr;
+  const int32_t *order = nullptr, *dynE = nullptr;
+  const uint32_t* rec = nullptr;
+  void *out = nullptr, *stream = nullptr;
+  int64_t E = 0, Ng = 0, slots = 0, kmod = 0, jmod = 0;
+  int C = 0, H0 = 0, W0 = 0, H1 = 0, W1 = 0, nlev = 2, gmap_pixel_major = 0;
+  float scale0 = 0.f, scale1 = 0.f, ref_mul = 1.0f;
+  int out_stride = 1, out_off = 0, out_pitch = 441;   // CorrArgs2: where element t of edge e goes
 };
 
-__global__ __launch_bounds__(256) void shadows_fingerprint_kernel(const ShadowJobs J) {
-  int b = (int)blockIdx.x;
-  for (int q = 0; q < J.n; q++) {               // workgroup-uniform
-    if (b < J.j[q].fp_blocks) {
-      fingerprint_body(reinterpret_cast<const uint32_t*>(J.j[q].src), J.j[q].words_per_slot, J.j[q].fp_new, b);
-      return;
-    }
-    b -= J.j[q].fp_blocks;
-  }
+template <int CC, int NLEV, bool REC>
+void launch_fused(int blocks, size_t smem2, hipStream_t s, const CorrArgs2& a) {
+  hipLaunchKernelGGL((corr_fused2_kernel<CC, NLEV, REC>), dim3(blocks), dim3(64 * CW), smem2, s, a.rec, a.dynE, a.E, blocks >> 3, a);
 }
 
-__global__ __launch_bounds__(256) void shadows_convert_kernel(const ShadowJobs J) {
-  int b = (int)blockIdx.x;
-  for (int q = 0; q < J.n; q++) {
-    const ShadowJob& s = J.j[q];
-    if (b < s.cv_blocks) {
-      dirty_body(s.src, s.dst, s.C, s.H, s.W, s.fp_new, s.fp_old, s.wg_per_slot, s.n_dirty, b);
-      return;
-    }
-    b -= s.cv_blocks;
-  }
-  if (J.g_src) cdv::gmap_pm_convert(J.g_src, J.g_dst, 0, J.g_count, J.g_C, (int64_t)b * 256 + threadIdx.x, (int64_t)J.g_blocks * 256);
-}
-
-__global__ __launch_bounds__(256) void gmap_pm_kernel(const _Float16* __restrict__ src, _Float16* __restrict__ dst,
-                                                      int64_t first, int64_t count, int C) {
-  cdv::gmap_pm_convert(src, dst, first, count, C, (int64_t)blockIdx.x * blockDim.x + threadIdx.x,
-                       (int64_t)gridDim.x * blockDim.x);
-}
-
-// feature-map ring write + 4x4 pool (+ the frame's patch tiles): body in cdv_parts.h
-__global__ __launch_bounds__(256) void fmap_ingest_kernel(cdv::IngestArgs a) {
-  cdv::ingest_body(a, (int)blockIdx.x, (int)blockDim.x, (int)threadIdx.x);
-}
-
-// patchify forward (correlation_kernel.cu:16-47): gather (2R+2)^2 tiles, zero when OOB
-template <typename T>
-__global__ __launch_bounds__(256) void patchify_kernel(const T* __restrict__ net, const float* __restrict__ coords,
-                                                       T* __restrict__ patches, int B, int64_t M, int C, int H, int W,
-                                                       int R) {
-  const int D = 2 * R + 2;
-  const int64_t total = (int64_t)B * M * C * D * D;
-  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
-       idx += (int64_t)gridDim.x * blockDim.x) {
-    int64_t t = idx;
-    const int b2 = (int)(t % D); t /= D;
-    const int a2 = (int)(t % D); t /= D;
-    const int ch = (int)(t % C); t /= C;
-    const int64_t m = t % M; t /= M;
-    const int bb = (int)t;
-    const float x = coords[(bb * M + m) * 2 + 0], y = coords[(bb * M + m) * 2 + 1];
-    const int i = (int)fminf(fmaxf(floorf(y), -1.0e6f), 1.0e6f) + (a2 - R);
-    const int j = (int)fminf(fmaxf(floorf(x), -1.0e6f), 1.0e6f) + (b2 - R);
-    T v = (T)0.f;
-    if (i >= 0 && i < H && j >= 0 && j < W) v = net[(((int64_t)bb * C + ch) * H + i) * W + j];
-    patches[idx] = v;
-  }
-}
-
-// altcorr.patchify(net, coords, radius, mode) (correlation.py:51-71) in one pass: mode 1 = 'bilinear' (the (2r+2)^2
-// gather of patchify_forward blended to (2r+1)^2 with the sub-pixel offset of the patch centre, in the reference's
-// operation order x00 + x01 + x10 + x11), mode 2 = 'upperleft' (the 1x1 corner tile).  Out-of-image taps are zero.
-// (the blend multiplies float32 offsets into the tile, so torch's type promotion makes the 'bilinear' result float32
-// whatever the map's dtype; 'upperleft' is a slice and keeps the dtype)
-template <typename T>
-__global__ __launch_bounds__(256) void patchify_blend_kernel(const T* __restrict__ net, const float* __restrict__ coords,
-                                                             void* __restrict__ outv, int B, int64_t M, int C, int H,
-                                                             int W, int R, int mode) {
-  const int d = (mode == 2) ? 1 : 2 * R + 1;
-  const int64_t total = (int64_t)B * M * C * d * d;
-  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
-       idx += (int64_t)gridDim.x * blockDim.x) {
-    int64_t t = idx;
-    const int b2 = (int)(t % d); t /= d;
-    const int a2 = (int)(t % d); t /= d;
-    const int ch = (int)(t % C); t /= C;
-    const int64_t m = t % M; t /= M;
-    const int bb = (int)t;
-    const float x = coords[(bb * M + m) * 2 + 0], y = coords[(bb * M + m) * 2 + 1];
-    const float fxf = floorf(x), fyf = floorf(y);
-    const int i0 = (int)fminf(fmaxf(fyf, -1.0e6f), 1.0e6f) + (a2 - R);
-    const int j0 = (int)fminf(fmaxf(fxf, -1.0e6f), 1.0e6f) + (b2 - R);
-    const T* np = net + ((int64_t)bb * C + ch) * H * W;
-    auto tap = [&](int i, int j) -> T { return (i >= 0 && i < H && j >= 0 && j < W) ? np[(int64_t)i * W + j] : (T)0.f; };
-    if (mode == 2) {
-      reinterpret_cast<T*>(outv)[idx] = tap(i0, j0);
-    } else {
-      const float dx = x - fxf, dy = y - fyf;   // correlation.py:58-66, same operation order
-      const float x00 = (1.0f - dy) * (1.0f - dx) * (float)tap(i0, j0);
-      const float x01 = (1.0f - dy) * dx * (float)tap(i0, j0 + 1);
-      const float x10 = dy * (1.0f - dx) * (float)tap(i0 + 1, j0);
-      const float x11 = dy * dx * (float)tap(i0 + 1, j0 + 1);
-      reinterpret_cast<float*>(outv)[idx] = ((x00 + x01) + x10) + x11;
-    }
-  }
-}
-
-// Several altcorr.patchify calls on ONE set of patch centres in one launch: a new frame's imap / gmap / colour / patch
-// tiles (net_cdv.py:355-374).  Job j reads its own map at (coords + o_j) * s_j -- the scaling the reference applies with
-// torch ops before each call (scale_f2i * coords, 4 * (coords + 0.5)), same two float operations -- with its own radius,
-// mode and dtype; workgroups [first[j], first[j + 1]) belong to job j.
-struct PatchifyJobs {
-  cdv_patchify_job j[CDV_MAX_PATCHIFY_JOBS];
-  int first[CDV_MAX_PATCHIFY_JOBS + 1];
-  int n_jobs;
-};
-
-template <typename T>
-__device__ __forceinline__ void patchify_job_body(const cdv_patchify_job& J, const float* __restrict__ coords, int64_t M,
-                                                  int64_t idx0, int64_t stride) {
-  const int R = J.radius, mode = J.mode, C = J.C, H = J.H, W = J.W;
-  const int d = (mode == 2) ? 1 : 2 * R + 1;
-  const int64_t total = M * C * d * d;
-  const T* net = reinterpret_cast<const T*>(J.net);
-  for (int64_t idx = idx0; idx < total; idx += stride) {
-    int64_t t = idx;
-    const int b2 = (int)(t % d); t /= d;
-    const int a2 = (int)(t % d); t /= d;
-    const int ch = (int)(t % C); t /= C;
-    const int64_t m = t;
-    const float x = (coords[m * 2 + 0] + J.ox) * J.sx, y = (coords[m * 2 + 1] + J.oy) * J.sy;
-    const float fxf = floorf(x), fyf = floorf(y);
-    const int i0 = (int)fminf(fmaxf(fyf, -1.0e6f), 1.0e6f) + (a2 - R);
-    const int j0 = (int)fminf(fmaxf(fxf, -1.0e6f), 1.0e6f) + (b2 - R);
-    const T* np = net + (int64_t)ch * H * W;
-    auto tap = [&](int i, int j) -> T { return (i >= 0 && i < H && j >= 0 && j < W) ? np[(int64_t)i * W + j] : (T)0.f; };
-    if (mode == 2) {
-      reinterpret_cast<T*>(J.out)[idx] = tap(i0, j0);
-    } else {
-      const float dx = x - fxf, dy = y - fyf;   // correlation.py:58-66, same operation order
-      const float x00 = (1.0f - dy) * (1.0f - dx) * (float)tap(i0, j0);
-      const float x01 = (1.0f - dy) * dx * (float)tap(i0, j0 + 1);
-      const float x10 = dy * (1.0f - dx) * (float)tap(i0 + 1, j0);
-      const float x11 = dy * dx * (float)tap(i0 + 1, j0 + 1);
-      reinterpret_cast<float*>(J.out)[idx] = ((x00 + x01) + x10) + x11;
-    }
-  }
-}
-
-__global__ __launch_bounds__(256) void patchify_multi_kernel(const PatchifyJobs P, const float* __restrict__ coords,
-                                                             int64_t M) {
-  int ji = 0;
-  while (ji + 1 < P.n_jobs && (int)blockIdx.x >= P.first[ji + 1]) ji++;
-  const cdv_patchify_job& J = P.j[ji];
-  const int nb = P.first[ji + 1] - P.first[ji];
-  const int64_t idx0 = (int64_t)((int)blockIdx.x - P.first[ji]) * 256 + threadIdx.x, stride = (int64_t)nb * 256;
-  if (J.dtype == CDV_F16) patchify_job_body<_Float16>(J, coords, M, idx0, stride);
-  else patchify_job_body<float>(J, coords, M, idx0, stride);
-}
-
-}  // namespace
-
-extern "C" int cdv_patchify_multi(const cdv_patchify_job* jobs, int n_jobs, const float* coords, int64_t M, void* stream) {
-  CDV_REQUIRE(n_jobs >= 0 && n_jobs <= CDV_MAX_PATCHIFY_JOBS, CDV_ERR_ARG, "cdv_patchify_multi: too many jobs");
-  if (n_jobs == 0 || M == 0) return CDV_OK;
-  CDV_REQUIRE(jobs != nullptr && coords != nullptr && M > 0, CDV_ERR_ARG, "cdv_patchify_multi: NULL argument");
-  PatchifyJobs P;
-  P.n_jobs = n_jobs;
-  P.first[0] = 0;
-  for (int i = 0; i < n_jobs; i++) {
-    const cdv_patchify_job& J = jobs[i];
-    CDV_REQUIRE(J.dtype == CDV_F16 || J.dtype == CDV_F32, CDV_ERR_UNSUPPORTED, "cdv_patchify_multi: dtype must be f16 or f32");
-    CDV_REQUIRE(J.mode == 1 || J.mode == 2, CDV_ERR_ARG, "cdv_patchify_multi: mode 1 (bilinear) or 2 (upperleft)");
-    CDV_REQUIRE(J.net && J.out && J.C > 0 && J.H > 0 && J.W > 0 && J.radius >= 0, CDV_ERR_ARG, "cdv_patchify_multi: bad job");
-    const int d = (J.mode == 2) ? 1 : 2 * J.radius + 1;
-    const int64_t total = M * J.C * d * d;
-    P.j[i] = J;
-    P.first[i + 1] = P.first[i] + (int)(cdv_div_up(total, 256) < 4096 ? cdv_div_up(total, 256) : 4096);
-  }
-  hipLaunchKernelGGL(patchify_multi_kernel, dim3(P.first[n_jobs]), dim3(256), 0, (hipStream_t)stream, P, coords, M);
-  CDV_LAUNCH_CHECK();
-  return CDV_OK;
-}
-
-extern "C" int cdv_patchify_blend(const void* net, const float* coords, void* out, int B, int64_t M, int C, int H, int W,
-                                  int radius, int mode, int dtype, void* stream) {
-  CDV_REQUIRE(dtype == CDV_F16 || dtype == CDV_F32, CDV_ERR_UNSUPPORTED, "cdv_patchify_blend: dtype must be f16 or f32");
-  CDV_REQUIRE(mode == 1 || mode == 2, CDV_ERR_ARG, "cdv_patchify_blend: mode 1 (bilinear) or 2 (upperleft)");
-  const int d = (mode == 2) ? 1 : 2 * radius + 1;
-  const int64_t total = (int64_t)B * M * C * d * d;
-  if (total == 0) return CDV_OK;
-  const int blocks = cdv_div_up(total, 256) < 16384 ? cdv_div_up(total, 256) : 16384;
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == CDV_F16)
-    hipLaunchKernelGGL(patchify_blend_kernel<_Float16>, dim3(blocks), dim3(256), 0, s, (const _Float16*)net, coords, out,
-                       B, M, C, H, W, radius, mode);
-  else
-    hipLaunchKernelGGL(patchify_blend_kernel<float>, dim3(blocks), dim3(256), 0, s, (const float*)net, coords, out, B, M,
-                       C, H, W, radius, mode);
-  CDV_LAUNCH_CHECK();
-  return CDV_OK;
-}
-
-extern "C" int cdv_corr_fwd(const void* fmap1, const void* fmap2, const float* coords, const int64_t* us,
-                            const int64_t* vs, void* out, int64_t M, int64_t N1, int64_t N2, int C, int P, int H2,
-                            int W2, int radius, int dtype, void* stream) {
-  CDV_REQUIRE(dtype == CDV_F16 || dtype == CDV_F32, CDV_ERR_UNSUPPORTED, "cdv_corr_fwd: dtype must be f16 or f32");
-  CDV_REQUIRE(C > 0 && P > 0 && radius >= 0 && H2 > 0 && W2 > 0, CDV_ERR_ARG, "cdv_corr_fwd: bad shape");
-  if (M == 0) return CDV_OK;
-  const int D1 = 2 * radius + 1;
-  const int64_t total = M * D1 * D1 * P * P;
-  const int blocks = cdv_div_up(total, 256) < 65536 ? cdv_div_up(total, 256) : 65536;
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == CDV_F16)
-    hipLaunchKernelGGL(corr_generic_kernel<_Float16>, dim3(blocks), dim3(256), 0, s, (const _Float16*)fmap1,
-                       (const _Float16*)fmap2, coords, us, vs, (_Float16*)out, M, N1, N2, C, P, H2, W2, radius);
-  else
-    hipLaunchKernelGGL(corr_generic_kernel<float>, dim3(blocks), dim3(256), 0, s, (const float*)fmap1,
-                       (const float*)fmap2, coords, us, vs, (float*)out, M, N1, N2, C, P, H2, W2, radius);
-  CDV_LAUNCH_CHECK();
-  return CDV_OK;
-}
-
-extern "C" size_t cdv_fmap_padded_elems(int64_t slots, int C, int H, int W) {
-  return (size_t)slots * (size_t)(H + 2 * PADY) * (size_t)(W + 2 * PADX) * (size_t)C;
-}
-
-extern "C" int cdv_fmap_to_nhwc(const void* src_nchw, void* dst_nhwc, int64_t N, int C, int H, int W, int64_t first,
-                                int64_t count, void* stream) {
-  CDV_REQUIRE(C % 8 == 0 && C > 0, CDV_ERR_ARG, "cdv_fmap_to_nhwc: C must be a multiple of 8");
-  CDV_REQUIRE(first >= 0 && count >= 0 && first + count <= N, CDV_ERR_ARG, "cdv_fmap_to_nhwc: slot range");
-  CDV_REQUIRE_ALIGNED(dst_nhwc, 16, "cdv_fmap_to_nhwc: dst_nhwc must be 16-byte aligned");
-  if (count == 0) return CDV_OK;
-  const int64_t total = count * H * W * (C / 8);
-  const int blocks = cdv_div_up(total, 256) < 16384 ? cdv_div_up(total, 256) : 16384;
-  hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const _Float16*)src_nchw,
-                     (_Float16*)dst_nhwc, first, count, C, H, W);
-  CDV_LAUNCH_CHECK();
-  return CDV_OK;
-}
-
-extern "C" size_t cdv_fmap_sync_workspace_bytes(int64_t N) {
-  return (size_t)(2 * (N > 0 ? N : 1) * FP_PARTS) * sizeof(uint64_t) + 64;
-}
-
-extern "C" int cdv_fmap_sync_nhwc(const void* src_nchw, void* dst_nhwc, int64_t N, int C, int H, int W, void* ws,
-                                  int parity, void* stream) {
-  CDV_REQUIRE(C % 8 == 0 && C > 0, CDV_ERR_ARG, "cdv_fmap_sync_nhwc: C must be a multiple of 8");
-  CDV_REQUIRE(src_nchw && dst_nhwc && ws && N >= 0 && H > 0 && W > 0, CDV_ERR_ARG, "cdv_fmap_sync_nhwc: bad argument");
-  CDV_REQUIRE_ALIGNED(dst_nhwc, 16, "cdv_fmap_sync_nhwc: dst_nhwc must be 16-byte aligned");
-  CDV_REQUIRE_ALIGNED(src_nchw, 4, "cdv_fmap_sync_nhwc: src_nchw must be 4-byte aligned");
-  CDV_REQUIRE_ALIGNED(ws, 16, "cdv_fmap_sync_nhwc: ws must be 16-byte aligned");
-  if (N == 0) return CDV_OK;
-  uint64_t* fp = (uint64_t*)ws;
-  uint64_t* fp_new = fp + (size_t)(parity & 1) * N * FP_PARTS;
-  const uint64_t* fp_old = fp + (size_t)((parity & 1) ^ 1) * N * FP_PARTS;
-  int32_t* n_dirty = (int32_t*)(fp + 2 * (size_t)N * FP_PARTS);
-  const int64_t words = (int64_t)C * H * W / 2;
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(fmap_fingerprint_kernel, dim3((unsigned)(N * FP_PARTS)), dim3(256), 0, s, (const uint32_t*)src_nchw,
-                     words, fp_new);
-  const int wg_per_slot = (int)(cdv_div_up((int64_t)H * W * (C / 8), 256) < 64 ? cdv_div_up((int64_t)H * W * (C / 8), 256) : 64);
-  hipLaunchKernelGGL(nchw_to_nhwc_dirty_kernel, dim3((unsigned)(N * wg_per_slot)), dim3(256), 0, s, (const _Float16*)src_nchw,
-                     (_Float16*)dst_nhwc, C, H, W, fp_new, fp_old, wg_per_slot, n_dirty);
-  CDV_LAUNCH_CHECK();
-  return CDV_OK;
-}
-
-extern "C" int cdv_shadows_sync(const cdv_shadow_ring* rings, int n_rings, const void* gmap_planar, void* gmap_pm, int64_t Ng,
-                                int C_tiles, void* stream) {
-  CDV_REQUIRE(n_rings >= 0 && n_rings <= 2 && (n_rings == 0 || rings != nullptr), CDV_ERR_ARG, "cdv_shadows_sync: 0 to 2 rings");
-  const bool do_g = gmap_planar != nullptr && gmap_pm != nullptr && Ng > 0;
-  CDV_REQUIRE(!do_g || (C_tiles % 8 == 0 && C_tiles > 0), CDV_ERR_ARG, "cdv_shadows_sync: C of the tiles must be a multiple of 8");
-  CDV_REQUIRE_ALIGNED(gmap_pm, 16, "cdv_shadows_sync: gmap_pm must be 16-byte aligned");
-  for (int q = 0; q < n_rings; q++) {
-    CDV_REQUIRE_ALIGNED(rings[q].dst_nhwc, 16, "cdv_shadows_sync: dst_nhwc must be 16-byte aligned");
-    CDV_REQUIRE_ALIGNED(rings[q].src_nchw, 4, "cdv_shadows_sync: src_nchw must be 4-byte aligned");
-    CDV_REQUIRE_ALIGNED(rings[q].ws, 16, "cdv_shadows_sync: ws must be 16-byte aligned");
-  }
-  ShadowJobs J;
-  J.n = 0;
-  int fp_total = 0, cv_total = 0;
-  for (int q = 0; q < n_rings; q++) {
-    const cdv_shadow_ring& r = rings[q];
-    CDV_REQUIRE(r.C % 8 == 0 && r.C > 0 && r.src_nchw && r.dst_nhwc && r.ws && r.N >= 0 && r.H > 0 && r.W > 0, CDV_ERR_ARG,
-                "cdv_shadows_sync: bad ring");
-    if (r.N == 0) continue;
-    ShadowJob& s = J.j[J.n++];
-    uint64_t* fp = (uint64_t*)r.ws;
-    s.src = (const _Float16*)r.src_nchw; s.dst = (_Float16*)r.dst_nhwc;
-    s.fp_new = fp + (size_t)(r.parity & 1) * r.N * FP_PARTS;
-    s.fp_old = fp + (size_t)((r.parity & 1) ^ 1) * r.N * FP_PARTS;
-    s.n_dirty = (int32_t*)(fp + 2 * (size_t)r.N * FP_PARTS);
-    s.words_per_slot = (int64_t)r.C * r.H * r.W / 2;
-    s.C = r.C; s.H = r.H; s.W = r.W;
-    const int64_t per = cdv_div_up((int64_t)r.H * r.W * (r.C / 8), 256);
-    s.wg_per_slot = (int)(per < 64 ? per : 64);
-    s.fp_blocks = (int)(r.N * FP_PARTS);
-    s.cv_blocks = (int)(r.N * s.wg_per_slot);
-    fp_total += s.fp_blocks; cv_total += s.cv_blocks;
-  }
-  J.g_src = do_g ? (const _Float16*)gmap_planar : nullptr;
-  J.g_dst = (_Float16*)gmap_pm;
-  J.g_count = Ng; J.g_C = C_tiles;
-  const int64_t gtotal = do_g ? Ng * 9 * (C_tiles / 8) : 0;
-  J.g_blocks = (int)(cdv_div_up(gtotal, 256) < 16384 ? cdv_div_up(gtotal, 256) : 16384);
-  if (!do_g) J.g_blocks = 0;
-  hipStream_t s = (hipStream_t)stream;
-  if (fp_total > 0) hipLaunchKernelGGL(shadows_fingerprint_kernel, dim3((unsigned)fp_total), dim3(256), 0, s, J);
-  if (cv_total + J.g_blocks > 0)
-    hipLaunchKernelGGL(shadows_convert_kernel, dim3((unsigned)(cv_total + J.g_blocks)), dim3(256), 0, s, J);
-  CDV_LAUNCH_CHECK();
-  return CDV_OK;
-}
-
-extern "C" int cdv_frame_ingest(const void* fmap_chw, void* fmap1_nhwc, void* fmap2_nhwc, void* fmap1_nchw,
-                                void* fmap2_nchw, int slot, int C, int H, int W, const void* gmap_planar, void* gmap_pm,
-                                int64_t Ng, int64_t gmap_first, int64_t gmap_count, void* stream) {
-  CDV_REQUIRE(C % 8 == 0 && C > 0, CDV_ERR_ARG, "cdv_fmap_ingest: C must be a multiple of 8");
-  CDV_REQUIRE(H % 4 == 0 && W % 4 == 0, CDV_ERR_ARG, "cdv_fmap_ingest: H and W must be multiples of 4");
-  CDV_REQUIRE(slot >= 0, CDV_ERR_ARG, "cdv_fmap_ingest: slot");
-  CDV_REQUIRE_ALIGNED(fmap1_nhwc, 16, "cdv_fmap_ingest: fmap1_nhwc must be 16-byte aligned");
-  CDV_REQUIRE_ALIGNED(fmap2_nhwc, 16, "cdv_fmap_ingest: fmap2_nhwc must be 16-byte aligned");
-  CDV_REQUIRE_ALIGNED(gmap_pm, 16, "cdv_frame_ingest: gmap_pm must be 16-byte aligned");
-  const bool do_g = gmap_planar != nullptr && gmap_pm != nullptr && gmap_count > 0;
-  CDV_REQUIRE(!do_g || (gmap_first >= 0 && gmap_first + gmap_count <= Ng), CDV_ERR_ARG, "cdv_frame_ingest: tile range");
-  const int64_t total = (int64_t)(H / 4) * (W / 4) * (C / 8) * 16;   // one thread per pixel and 8-channel group
-  const int blocks = cdv_div_up(total, 256);
-  const int gblocks = do_g ? (int)cdv_div_up(gmap_count * 9 * (C / 8), 256) : 0;
-  const cdv::IngestArgs a{(const _Float16*)fmap_chw, (_Float16*)fmap1_nhwc, (_Float16*)fmap2_nhwc, (_Float16*)fmap1_nchw,
-                          (_Float16*)fmap2_nchw, slot, C, H, W, (const _Float16*)gmap_planar, (_Float16*)gmap_pm,
-                          gmap_first, gmap_count, blocks, gblocks};
-  hipLaunchKernelGGL(fmap_ingest_kernel, dim3(blocks + gblocks), dim3(256), 0, (hipStream_t)stream, a);
-  CDV_LAUNCH_CHECK();
-  return CDV_OK;
-}
-
-extern "C" int cdv_fmap_ingest(const void* fmap_chw, void* fmap1_nhwc, void* fmap2_nhwc, void* fmap1_nchw,
-                               void* fmap2_nchw, int slot, int C, int H, int W, void* stream) {
-  return cdv_frame_ingest(fmap_chw, fmap1_nhwc, fmap2_nhwc, fmap1_nchw, fmap2_nchw, slot, C, H, W, nullptr, nullptr, 0,
-                          0, 0, stream);
-}
-
-extern "C" int cdv_gmap_to_pixel_major(const void* gmap_planar, void* gmap_pm, int64_t Ng, int C, int64_t first,
-                                       int64_t count, void* stream) {
-  CDV_REQUIRE(C % 8 == 0 && C > 0, CDV_ERR_ARG, "cdv_gmap_to_pixel_major: C must be a multiple of 8");
-  CDV_REQUIRE(first >= 0 && count >= 0 && first + count <= Ng, CDV_ERR_ARG, "cdv_gmap_to_pixel_major: tile range");
-  CDV_REQUIRE_ALIGNED(gmap_pm, 16, "cdv_gmap_to_pixel_major: gmap_pm must be 16-byte aligned");
-  if (count == 0) return CDV_OK;
-  const int64_t total = count * 9 * (C / 8);
-  const int blocks = cdv_div_up(total, 256) < 16384 ? cdv_div_up(total, 256) : 16384;
-  hipLaunchKernelGGL(gmap_pm_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const _Float16*)gmap_planar,
-                     (_Float16*)gmap_pm, first, count, C);
-  CDV_LAUNCH_CHECK();
-  return CDV_OK;
-}
-
-static int corr_fused_impl(const void* gmap, const void* fmap0_nhwc, const void* fmap1_nhwc, const float* coords,
-                           const int64_t* kk, const int64_t* jj, const int32_t* order, void* out, int64_t E,
-                           int64_t Ng, int64_t slots, int C, int H0, int W0, int H1, int W1, float scale0,
-                           float scale1, int nlev, int64_t kmod, int64_t jmod, int gmap_pixel_major, void* stream,
-                           int out_stride, int out_off, int out_pitch, const float* coords_ref, float ref_mul,
-                           const uint32_t* rec = nullptr, const int32_t* dynE = nullptr) {
+int corr_fused_impl(const FusedCall& c) {
+  const int C = c.C, nlev = c.nlev;
   CDV_REQUIRE(nlev == 1 || nlev == 2, CDV_ERR_ARG, "cdv_corr_fused: nlev must be 1 or 2");
   CDV_REQUIRE(C % 8 == 0 && C > 0 && C <= 128, CDV_ERR_UNSUPPORTED, "cdv_corr_fused: C must be a multiple of 8, <= 128");
-  CDV_REQUIRE(E >= 0 && E < ((int64_t)1 << 31), CDV_ERR_ARG, "cdv_corr_fused: E out of range");
+  CDV_REQUIRE(c.E >= 0 && c.E < ((int64_t)1 << 31), CDV_ERR_ARG, "cdv_corr_fused: E out of range");
   int ex0 = 0, ex1 = 0;
-  CDV_REQUIRE(scale0 > 0.f && frexpf(scale0, &ex0) == 0.5f && (nlev == 1 || (scale1 > 0.f && frexpf(scale1, &ex1) == 0.5f)),
+  CDV_REQUIRE(c.scale0 > 0.f && frexpf(c.scale0, &ex0) == 0.5f && (nlev == 1 || (c.scale1 > 0.f && frexpf(c.scale1, &ex1) == 0.5f)),
               CDV_ERR_UNSUPPORTED, "cdv_corr_fused: pyramid scales must be powers of two (1 and 4 in SLAM.corr)");
-  CDV_REQUIRE(fmap0_nhwc != nullptr && (nlev == 1 || fmap1_nhwc != nullptr), CDV_ERR_ARG, "cdv_corr_fused: NULL map");
-  CDV_REQUIRE_ALIGNED(fmap0_nhwc, 16, "cdv_corr_fused: fmap0_nhwc must be 16-byte aligned");
-  CDV_REQUIRE_ALIGNED(nlev == 2 ? fmap1_nhwc : nullptr, 16, "cdv_corr_fused: fmap1_nhwc must be 16-byte aligned");
-  CDV_REQUIRE_ALIGNED(gmap_pixel_major ? gmap : nullptr, 16, "cdv_corr_fused: pixel-major gmap must be 16-byte aligned");
-  CDV_REQUIRE_ALIGNED(out, 4, "cdv_corr_fused: out must be 4-byte aligned");
-  CDV_REQUIRE(cdv_fmap_padded_elems(slots, C, H0, W0) * 2 < ((size_t)1 << 32) &&
-                  (nlev == 1 || cdv_fmap_padded_elems(slots, C, H1, W1) * 2 < ((size_t)1 << 32)),
+  CDV_REQUIRE(c.fmap0_nhwc != nullptr && (nlev == 1 || c.fmap1_nhwc != nullptr), CDV_ERR_ARG, "cdv_corr_fused: NULL map");
+  CDV_REQUIRE_ALIGNED(c.fmap0_nhwc, 16, "cdv_corr_fused: fmap0_nhwc must be 16-byte aligned");
+  CDV_REQUIRE_ALIGNED(nlev == 2 ? c.fmap1_nhwc : nullptr, 16, "cdv_corr_fused: fmap1_nhwc must be 16-byte aligned");
+  CDV_REQUIRE_ALIGNED(c.gmap_pixel_major ? c.gmap : nullptr, 16, "cdv_corr_fused: pixel-major gmap must be 16-byte aligned");
+  CDV_REQUIRE_ALIGNED(c.out, 4, "cdv_corr_fused: out must be 4-byte aligned");
+  CDV_REQUIRE(cdv_fmap_padded_elems(c.slots, C, c.H0, c.W0) * 2 < ((size_t)1 << 32) &&
+                  (nlev == 1 || cdv_fmap_padded_elems(c.slots, C, c.H1, c.W1) * 2 < ((size_t)1 << 32)),
               CDV_ERR_UNSUPPORTED, "cdv_corr_fused: a feature ring of 4 GB or more");
-  CDV_REQUIRE(kmod >= 0 && jmod >= 0 && kmod < ((int64_t)1 << 31) && jmod < ((int64_t)1 << 31), CDV_ERR_ARG,
+  CDV_REQUIRE(c.kmod >= 0 && c.jmod >= 0 && c.kmod < ((int64_t)1 << 31) && c.jmod < ((int64_t)1 << 31), CDV_ERR_ARG,
               "cdv_corr_fused: kmod / jmod out of range");
   // ceil(2^32 / d): mulhi(x, magic) is x / d or x / d + 1 for 0 <= x < 2^31
-  const uint32_t kmagic = kmod > 1 ? (uint32_t)((((uint64_t)1 << 32) + (uint64_t)kmod - 1) / (uint64_t)kmod) : 0u;
-  const uint32_t jmagic = jmod > 1 ? (uint32_t)((((uint64_t)1 << 32) + (uint64_t)jmod - 1) / (uint64_t)jmod) : 0u;
-  if (E == 0) return CDV_OK;
+  const uint32_t kmagic = c.kmod > 1 ? (uint32_t)((((uint64_t)1 << 32) + (uint64_t)c.kmod - 1) / (uint64_t)c.kmod) : 0u;
+  const uint32_t jmagic = c.jmod > 1 ? (uint32_t)((((uint64_t)1 << 32) + (uint64_t)c.jmod - 1) / (uint64_t)c.jmod) : 0u;
+  if (c.E == 0) return CDV_OK;
   CDV_REQUIRE(nlev == 1 || ex1 >= ex0, CDV_ERR_UNSUPPORTED, "cdv_corr_fused: level 1 must not be finer than level 0");
-  const size_t smem = 4 * (size_t)(C <= 32 ? WAVE_LDS2_BYTES : WAVE_LDS_BYTES);
   static const int exp = getenv("CDV_CORR_EXP") ? atoi(getenv("CDV_CORR_EXP")) : 0;  // diagnostics only
-  hipStream_t s = (hipStream_t)stream;
+  hipStream_t s = (hipStream_t)c.stream;
   if (C <= 32) {
-    CDV_REQUIRE(Ng < ((int64_t)1 << 31) && slots < ((int64_t)1 << 31) && (size_t)Ng * 9 * (size_t)C * 2 < ((size_t)1 << 32),
+    CDV_REQUIRE(c.Ng < ((int64_t)1 << 31) && c.slots < ((int64_t)1 << 31) && (size_t)c.Ng * 9 * (size_t)C * 2 < ((size_t)1 << 32),
                 CDV_ERR_UNSUPPORTED, "cdv_corr_fused: 4 GB or more of patch tiles");
     auto level = [&](const void* ring, int H, int W, float scale, int shift) {
       const uint32_t pitch = (uint32_t)(W + 2 * PADX) * (uint32_t)C * 2u;
       return CorrLevel{(const char*)ring - (size_t)FBIAS, H, W, 1.0f / scale, shift, pitch, pitch * (uint32_t)(H + 2 * PADY)};
     };
-    const CorrLevel A0 = level(fmap0_nhwc, H0, W0, scale0, 0);
-    const CorrArgs2 a{coords, kk, jj, order, (int)E, (uint32_t)kmod, (uint32_t)jmod, kmagic, jmagic, (uint32_t)Ng,
-                      (uint32_t)slots, (const char*)gmap, (_Float16*)out, A0,
-                      nlev == 2 ? level(fmap1_nhwc, H1, W1, scale1, ex1 - ex0) : A0, C, gmap_pixel_major, exp,
-                      out_stride, out_off, out_pitch, coords_ref, ref_mul, rec, dynE};
-    const int blocks = 8 * (int)cdv_div_up(E, 8 * CW);   // a multiple of 8: the kernel deals contiguous eighths to the XCDs
+    const CorrLevel A0 = level(c.fmap0_nhwc, c.H0, c.W0, c.scale0, 0);
+    const CorrArgs2 a{c.coords, c.kk, c.jj, c.order, (int)c.E, (uint32_t)c.kmod, (uint32_t)c.jmod, kmagic, jmagic, (uint32_t)c.Ng,
+                      (uint32_t)c.slots, (const char*)c.gmap, (_Float16*)c.out, A0,
+                      nlev == 2 ? level(c.fmap1_nhwc, c.H1, c.W1, c.scale1, ex1 - ex0) : A0, C, c.gmap_pixel_major, exp,
+                      c.out_stride, c.out_off, c.out_pitch, c.coords_ref, c.ref_mul, c.rec, c.dynE};
+    const int blocks = 8 * (int)cdv_div_up(c.E, 8 * CW);   // a multiple of 8: the kernel deals contiguous eighths to the XCDs
     const size_t smem2 = (size_t)CW * WAVE_LDS2_BYTES;
-    if (rec) {   // packed input stream in processing order (cdv_corr_fused_stream)
-      CDV_REQUIRE(nlev == 2 && coords_ref == nullptr, CDV_ERR_UNSUPPORTED, "cdv_corr_fused_stream: two fused levels only");
-      if (C == 24) hipLaunchKernelGGL((corr_fused2_kernel<24, 2, true>), dim3(blocks), dim3(64 * CW), smem2, s, rec, dynE, (int)E, blocks >> 3, a);
-      else hipLaunchKernelGGL((corr_fused2_kernel<0, 2, true>), dim3(blocks), dim3(64 * CW), smem2, s, rec, dynE, (int)E, blocks >> 3, a);
-    } else if (nlev == 2 && C == 24)
-      hipLaunchKernelGGL((corr_fused2_kernel<24, 2>), dim3(blocks), dim3(64 * CW), smem2, s, rec, dynE, (int)E, blocks >> 3, a);
-    else if (nlev == 2)
-      hipLaunchKernelGGL((corr_fused2_kernel<0, 2>), dim3(blocks), dim3(64 * CW), smem2, s, rec, dynE, (int)E, blocks >> 3, a);
-    else if (C == 24)   // one level per call: what an unchanged slam.py issues (slam.py:316-323), twice per update
-      hipLaunchKernelGGL((corr_fused2_kernel<24, 1>), dim3(blocks), dim3(64 * CW), smem2, s, rec, dynE, (int)E, blocks >> 3, a);
-    else
-      hipLaunchKernelGGL((corr_fused2_kernel<0, 1>), dim3(blocks), dim3(64 * CW), smem2, s, rec, dynE, (int)E, blocks >> 3, a);
+    if (c.rec) {   // packed input stream in processing order (cdv_corr_fused_stream)
+      CDV_REQUIRE(nlev == 2 && c.coords_ref == nullptr, CDV_ERR_UNSUPPORTED, "cdv_corr_fused_stream: two fused levels only");
+      C == 24 ? launch_fused<24, 2, true>(blocks, smem2, s, a) : launch_fused<0, 2, true>(blocks, smem2, s, a);
+    } else if (nlev == 2) {
+      C == 24 ? launch_fused<24, 2, false>(blocks, smem2, s, a) : launch_fused<0, 2, false>(blocks, smem2, s, a);
+    } else {   // one level per call: what an unchanged slam.py issues (slam.py:316-323), twice per update
+      C == 24 ? launch_fused<24, 1, false>(blocks, smem2, s, a) : launch_fused<0, 1, false>(blocks, smem2, s, a);
+    }
   } else {
-    CDV_REQUIRE(out_stride == 1 && out_off == 0 && coords_ref == nullptr, CDV_ERR_UNSUPPORTED,
+    CDV_REQUIRE(c.out_stride == 1 && c.out_off == 0 && c.coords_ref == nullptr, CDV_ERR_UNSUPPORTED,
                 "cdv_corr_fused: checked calls need C <= 32");
-    LevelParams L0{(const _Float16*)fmap0_nhwc, H0, W0, 1.0f / scale0, 0};
-    LevelParams L1{(const _Float16*)fmap1_nhwc, H1, W1, nlev == 2 ? 1.0f / scale1 : 1.0f, nlev == 2 ? ex1 - ex0 : 0};
-    hipLaunchKernelGGL(corr_wide_kernel<4>, dim3(cdv_div_up(E, 4)), dim3(256), smem, s, (const _Float16*)gmap, L0, L1, coords,
-                       kk, jj, order, (_Float16*)out, (int)E, Ng, slots, C, nlev, kmod, jmod, kmagic, jmagic,
-                       gmap_pixel_major, exp);
+    LevelParams L0{(const _Float16*)c.fmap0_nhwc, c.H0, c.W0, 1.0f / c.scale0, 0};
+    LevelParams L1{(const _Float16*)c.fmap1_nhwc, c.H1, c.W1, nlev == 2 ? 1.0f / c.scale1 : 1.0f, nlev == 2 ? ex1 - ex0 : 0};
+    hipLaunchKernelGGL(corr_wide_kernel<4>, dim3(cdv_div_up(c.E, 4)), dim3(256), 4 * (size_t)WAVE_LDS_BYTES, s, (const _Float16*)c.gmap,
+                       L0, L1, c.coords, c.kk, c.jj, c.order, (_Float16*)c.out, (int)c.E, c.Ng, c.slots, C, nlev, c.kmod, c.jmod,
+                       kmagic, jmagic, c.gmap_pixel_major, exp);
   }
   CDV_LAUNCH_CHECK();
   return CDV_OK;
 }
 
+}  // namespace
+
 extern "C" int cdv_corr_fused(const void* gmap, const void* fmap0_nhwc, const void* fmap1_nhwc, const float* coords,
                               const int64_t* kk, const int64_t* jj, const int32_t* order, void* out, int64_t E,
                               int64_t Ng, int64_t slots, int C, int H0, int W0, int H1, int W1, float scale0,
                               float scale1, int nlev, int64_t kmod, int64_t jmod, int gmap_pixel_major, void* stream) {
-  return corr_fused_impl(gmap, fmap0_nhwc, fmap1_nhwc, coords, kk, jj, order, out, E, Ng, slots, C, H0, W0, H1, W1, scale0,
-                         scale1, nlev, kmod, jmod, gmap_pixel_major, stream, 1, 0, 441, nullptr, 1.0f);
+  FusedCall c;
+  c.gmap = gmap; c.fmap0_nhwc = fmap0_nhwc; c.fmap1_nhwc = fmap1_nhwc; c.out = out; c.E = E; c.Ng = Ng; c.slots = slots;
+  c.C = C; c.H0 = H0; c.W0 = W0; c.H1 = H1; c.W1 = W1; c.scale0 = scale0; c.scale1 = scale1;
+  c.gmap_pixel_major = gmap_pixel_major; c.stream = stream;
+  c.coords = coords; c.kk = kk; c.jj = jj; c.order = order; c.nlev = nlev; c.kmod = kmod; c.jmod = jmod;
+  return corr_fused_impl(c);
 }
 
 extern "C" int cdv_corr_fused_stream(const void* gmap, const void* fmap0_nhwc, const void* fmap1_nhwc, const void* records,
@@ -1402,9 +920,12 @@ extern "C" int cdv_corr_fused_stream(const void* gmap, const void* fmap0_nhwc, c
                                      float scale0, float scale1, int gmap_pixel_major, void* stream) {
   CDV_REQUIRE(records != nullptr, CDV_ERR_ARG, "cdv_corr_fused_stream: NULL record stream");
   CDV_REQUIRE(C <= 32, CDV_ERR_UNSUPPORTED, "cdv_corr_fused_stream: C must be <= 32");
-  return corr_fused_impl(gmap, fmap0_nhwc, fmap1_nhwc, nullptr, nullptr, nullptr, nullptr, out, E, Ng, slots, C, H0, W0, H1,
-                         W1, scale0, scale1, 2, 0, 0, gmap_pixel_major, stream, 1, 0, 441, nullptr, 1.0f,
-                         (const uint32_t*)records);
+  FusedCall c;
+  c.gmap = gmap; c.fmap0_nhwc = fmap0_nhwc; c.fmap1_nhwc = fmap1_nhwc; c.out = out; c.E = E; c.Ng = Ng; c.slots = slots;
+  c.C = C; c.H0 = H0; c.W0 = W0; c.H1 = H1; c.W1 = W1; c.scale0 = scale0; c.scale1 = scale1;
+  c.gmap_pixel_major = gmap_pixel_major; c.stream = stream;
+  c.rec = (const uint32_t*)records;
+  return corr_fused_impl(c);
 }
 
 // cdv_corr_fused_stream with the number of edges on the device: *dyn_E edges (at most E_bound, which sizes the launch)
@@ -1413,9 +934,12 @@ extern "C" int cdv_corr_fused_stream_dyn(const void* gmap, const void* fmap0_nhw
                                          int W0, int H1, int W1, float scale0, float scale1, int gmap_pixel_major, void* stream) {
   CDV_REQUIRE(records != nullptr && dyn != nullptr, CDV_ERR_ARG, "cdv_corr_fused_stream_dyn: NULL record stream / dynamic block");
   CDV_REQUIRE(C <= 32, CDV_ERR_UNSUPPORTED, "cdv_corr_fused_stream_dyn: C must be <= 32");
-  return corr_fused_impl(gmap, fmap0_nhwc, fmap1_nhwc, nullptr, nullptr, nullptr, nullptr, out, E_bound, Ng, slots, C, H0, W0,
-                         H1, W1, scale0, scale1, 2, 0, 0, gmap_pixel_major, stream, 1, 0, 441, nullptr, 1.0f,
-                         (const uint32_t*)records, dyn + CDV_DYN_E);
+  FusedCall c;
+  c.gmap = gmap; c.fmap0_nhwc = fmap0_nhwc; c.fmap1_nhwc = fmap1_nhwc; c.out = out; c.E = E_bound; c.Ng = Ng; c.slots = slots;
+  c.C = C; c.H0 = H0; c.W0 = W0; c.H1 = H1; c.W1 = W1; c.scale0 = scale0; c.scale1 = scale1;
+  c.gmap_pixel_major = gmap_pixel_major; c.stream = stream;
+  c.rec = (const uint32_t*)records; c.dynE = dyn + CDV_DYN_E;
+  return corr_fused_impl(c);
 }
 
 // ONE level of the INTERLEAVED two-level result of cdv_corr_fused ([E][441][2] halves: what SLAM.corr's torch.stack(..., -1)
@@ -1428,24 +952,11 @@ extern "C" int cdv_corr_level_checked_interleaved(const void* gmap, const void* 
   CDV_REQUIRE(level == 0 || level == 1, CDV_ERR_ARG, "cdv_corr_level_checked_interleaved: level must be 0 or 1");
   CDV_REQUIRE(coords_ref != nullptr && out != nullptr, CDV_ERR_ARG, "cdv_corr_level_checked_interleaved: NULL argument");
   CDV_REQUIRE(C <= 32, CDV_ERR_UNSUPPORTED, "cdv_corr_level_checked_interleaved: C must be <= 32");
-  return corr_fused_impl(gmap, fmap_nhwc, nullptr, coords, kk, jj, nullptr, out, E, Ng, slots, C, H, W, 0, 0, scale, 1.0f, 1,
-                         kmod, jmod, gmap_pixel_major, stream, 2, level, 882, coords_ref, ref_mul);
-}
-
-extern "C" int cdv_patchify_fwd(const void* net, const float* coords, void* patches, int B, int64_t M, int C, int H,
-                                int W, int radius, int dtype, void* stream) {
-  CDV_REQUIRE(dtype == CDV_F16 || dtype == CDV_F32, CDV_ERR_UNSUPPORTED, "cdv_patchify_fwd: dtype must be f16 or f32");
-  const int D = 2 * radius + 2;
-  const int64_t total = (int64_t)B * M * C * D * D;
-  if (total == 0) return CDV_OK;
-  const int blocks = cdv_div_up(total, 256) < 16384 ? cdv_div_up(total, 256) : 16384;
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == CDV_F16)
-    hipLaunchKernelGGL(patchify_kernel<_Float16>, dim3(blocks), dim3(256), 0, s, (const _Float16*)net, coords,
-                       (_Float16*)patches, B, M, C, H, W, radius);
-  else
-    hipLaunchKernelGGL(patchify_kernel<float>, dim3(blocks), dim3(256), 0, s, (const float*)net, coords,
-                       (float*)patches, B, M, C, H, W, radius);
-  CDV_LAUNCH_CHECK();
-  return CDV_OK;
+  FusedCall c;
+  c.gmap = gmap; c.fmap0_nhwc = fmap_nhwc; c.out = out; c.E = E; c.Ng = Ng; c.slots = slots;
+  c.C = C; c.H0 = H; c.W0 = W; c.scale0 = scale; c.scale1 = 1.0f;
+  c.gmap_pixel_major = gmap_pixel_major; c.stream = stream;
+  c.coords = coords; c.kk = kk; c.jj = jj; c.nlev = 1; c.kmod = kmod; c.jmod = jmod;
+  c.out_stride = 2; c.out_off = level; c.out_pitch = 882; c.coords_ref = coords_ref; c.ref_mul = ref_mul;
+  return corr_fused_impl(c);
 }

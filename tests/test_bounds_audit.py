@@ -329,7 +329,7 @@ def _to_ring(planar):
 
 @pytest.mark.parametrize("C", [8, 24])
 def test_gmap_to_pixel_major(C):
-    # corr.hip gmap_pm_kernel: one lane per (tile, pixel, 8-channel group), 256 lanes: 9 C / 8 lanes per tile
+    # rings.hip gmap_pm_kernel: one lane per (tile, pixel, 8-channel group), 256 lanes: 9 C / 8 lanes per tile
     per = 9 * C // 8
     sizes = sorted({1, 2, 256 // per, 256 // per + 1, 512 // per + 1, 1009})
     for Ng in sizes:
@@ -351,7 +351,7 @@ def test_gmap_to_pixel_major(C):
 
 @pytest.mark.parametrize("C", [8, 24])
 def test_fmap_to_nhwc(C):
-    # corr.hip nchw_to_nhwc_kernel: one lane per (slot, pixel, 8-channel group), 256 lanes; H x W = 4 x 4: 16 C / 8 lanes a slot
+    # rings.hip nchw_to_nhwc_kernel: one lane per (slot, pixel, 8-channel group), 256 lanes; H x W = 4 x 4: 16 C / 8 lanes a slot
     H, W = 4, 4
     per = H * W * C // 8
     for count_all in sorted({1, 256 // per - 1, 256 // per, 256 // per + 1, 512 // per + 1, 67}):
@@ -378,7 +378,7 @@ def _pool4(f):
 @pytest.mark.parametrize("with_tiles", [False, True])
 def test_ingest(with_tiles):
     """cdv_fmap_ingest / cdv_frame_ingest: the first and the LAST ring slot, with and without the planar rings, tile ranges
-    at both ends of the tile array.  corr.hip fmap_ingest_kernel: (H/4)(W/4)(C/8) * 16 lanes, 256 a workgroup."""
+    at both ends of the tile array.  rings.hip fmap_ingest_kernel: (H/4)(W/4)(C/8) * 16 lanes, 256 a workgroup."""
     from tests.stream_audit import f16_ulps
     C, slots, Ng = 8, 3, 40
     for H, W in ((4, 4), (12, 20), (16, 16), (16, 20)):      # 16, 240, 256, 320 lanes
@@ -603,7 +603,7 @@ def test_corr_level_checked(C, pm, level):
 @pytest.mark.parametrize("dtype", [np.float16, np.float32])
 @pytest.mark.parametrize("radius,Pp", [(1, 3), (3, 3), (0, 4)])
 def test_corr_fwd(dtype, radius, Pp):
-    # corr.hip corr_generic_kernel: one lane per output element, 256 lanes; an edge has P^2 (2 r + 1)^2 of them.  With 3 x 3
+    # altcorr_fwd.hip corr_generic_kernel: one lane per output element, 256 lanes; an edge has P^2 (2 r + 1)^2 of them.  With 3 x 3
     # patches that is odd and never fills a workgroup exactly; P = 4, r = 0 gives 16 per edge: M = 15 / 16 / 17 are one short of,
     # exactly and one over 256 lanes
     D1 = 2 * radius + 1
