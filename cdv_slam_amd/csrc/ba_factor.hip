@@ -1,7 +1,7 @@
 // ba_factor.hip -- the Cholesky factorisation of the global bundle adjustment's reduced system (32 < N <= 1024 free poses,
 // the dense `torch.linalg.cholesky` of 6N unknowns behind ba_cuda.cu:567-594 / slam.py:460-478) as ONE launch.
 //
-// The matrix A [(npad + 1)][npad] (ba.hip ba_big_fold_kernel: S with the damping of ba_cuda.cu:589, identity on the padded
+// The matrix A [(npad + 1)][npad] (ba_big.hip ba_big_fold_kernel: S with the damping of ba_cuda.cu:589, identity on the padded
 // diagonal, row npad = y^T) is cut into 64 x 64 blocks; the result -- L in the lower blocks, z = L^-1 y in the last row --
 // is what ba_big_backsolve_kernel reads.  Rounds 1-3 ran one launch per block column (28 x 26 us at N = 299: a one-wave
 // panel chain behind a launch boundary each).  Here a block is computed LEFT-LOOKING,

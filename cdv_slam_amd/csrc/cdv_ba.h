@@ -1,5 +1,5 @@
-// cdv_ba.h -- internal: workspace layout and launch interface shared by ba.hip (dispatch, larger systems) and
-// ba_win.hip (the optimisation-window path, N <= 10 free poses).
+// cdv_ba.h -- internal: workspace layout and launch interface shared by ba.hip (entry point, dispatch) and the three paths
+// it dispatches to: ba_win.hip (N <= 10 free poses), ba_mid.hip (10 < N <= 32) and ba_big.hip (N > 32, N = 0).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -176,6 +176,42 @@ __device__ __forceinline__ BaWinArgs with_dyn(const BaWinArgs& a) {
 // factors in the layout the item workgroups solve against)
 int cdv_ba_big_factor(float* A, int npad, int32_t* ctl, float* ltg, const int32_t* gmeta, int32_t* info, int test, hipStream_t s);
 int cdv_ba_big_factor_items(int nb);
+
+// Arguments of the dense path (ba_big.hip: N > 32 free poses, and N = 0).  ba.hip fills it once per call from the workspace
+// layout and the patch index, and sets first, token and dbg per iteration.
+struct BaDenseArgs {
+  float *poses, *patches;
+  const float *intr, *target, *weight, *lmbda;
+  const int64_t *ii, *jj, *kk;
+  int64_t E;
+  int P, t0, N;
+  const int32_t *gmeta, *prec, *koff_u;   // the patch index (ranked)
+  const int64_t* kx;
+  float *sy, *dXg, *Cg, *ug, *qg, *Edg;   // areas of the workspace (BaLayout)
+  uint32_t* cmask;                        // NULL when N = 0
+  float* Abig;
+  uint64_t* xgran;
+  int32_t* fctl;
+  float* ltg;
+  int32_t* ptab;                          // N > 32: pair table, pair partials, pair keys, the frame-pair index's own workspace
+  float* pdiag;
+  int64_t* pkeys;
+  void* pgraph;
+  size_t pgraph_bytes;
+  int64_t E_max, pair_range, pair_cap;
+  int64_t U_stride, U_max, sy_stride, npad;
+  int32_t* info;
+  int32_t* counters;                      // optional host-visible event counters (cdv_ba_bind_status_counters), may be NULL
+  int test;                               // HO_TEST_*: hand-off fault injection (tests only), 0 in production
+  float* dbg;                             // iteration-0 dump (see cdv_ba_forward), may be NULL
+  int token;                              // tag of this iteration's back-substitution hand-offs: never 0, new per iteration
+  int first;                              // first iteration of a call: clears the sticky status words
+};
+
+// the frame-pair index of a call with more than 32 free poses, built once in front of its iterations (fresh: the first call
+// on this workspace in this layout), and one Gauss-Newton iteration of the dense path
+int cdv_ba_dense_pair_index(const BaDenseArgs& a, bool fresh, hipStream_t s);
+int cdv_ba_dense_iteration(const BaDenseArgs& a, hipStream_t s);
 
 // one Gauss-Newton iteration of the window path: two launches on `s`
 int cdv_ba_window_iteration(const BaWinArgs& a, hipStream_t s);

@@ -36,6 +36,12 @@ void cdv_set_error(int code, const char* msg);
 
 static inline int cdv_div_up(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
+// ceil(2^32 / mod), the reciprocal the kernels reduce ring indices with: __umulhi(x, magic) is x / mod or x / mod + 1 for
+// 0 <= x < 2^31 (0 for mod <= 1, which the kernels treat apart)
+static inline uint32_t cdv_magic_u32(int64_t mod) {
+  return mod > 1 ? (uint32_t)((((uint64_t)1 << 32) + (uint64_t)mod - 1) / (uint64_t)mod) : 0u;
+}
+
 typedef _Float16 cdv_half8 __attribute__((ext_vector_type(8)));
 typedef float cdv_float4 __attribute__((ext_vector_type(4)));
 

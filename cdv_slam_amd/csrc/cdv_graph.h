@@ -56,6 +56,8 @@ struct CorrStream {
   uint32_t kmod, jmod, kmagic, jmagic, Ng, slots;
   float inv_scale0;      // 1 / scale of pyramid level 0 (slam.py:321: 1)
 };
+// no stream bound: the builds write no packed records (members in declaration order; the one place that spells them out)
+constexpr CorrStream CORR_STREAM_NONE = {nullptr, 0, 0, 0, 0, 0, 0, 1.0f};
 
 struct GraphLayout {
   int64_t E_max, k_range;
@@ -154,21 +156,23 @@ static inline GraphView graph_view(void* ws, const GraphLayout& L) {
 
 }  // namespace cdv
 
-// host-side registry: workspace pointer -> layout (filled by cdv_graph_build)
-bool cdv_graph_lookup(const void* ws, cdv::GraphLayout* out);
+// host-side registry (graph.hip): what the library knows about the index in a workspace, copied out under ONE lock so that
+// the answers describe the same build
+namespace cdv {
+struct GraphInfo {
+  GraphLayout L;
+  bool has_ii;        // the last build was given the source frames ii (they are then part of the edge records)
+  bool table;         // the index is a patch table (cdv_graph_build_table) ...
+  int32_t tab_cap;    // ... of this capacity in slots (0: not a table)
+};
+}  // namespace cdv
+// false: the workspace holds no built or initialised index (*out is then left alone)
+bool cdv_graph_info(const void* ws, cdv::GraphInfo* out);
 
 void cdv_graph_forget(const void* ws);
 
 // builds on this workspace skip the correlation's processing order (an index no correlation walks; forgotten with the workspace)
 void cdv_graph_no_corr_order(const void* ws);
-
-// was the last build on this workspace given the source frames ii (they are then part of the edge records)?
-bool cdv_graph_has_ii(const void* ws);
-
-// is the index in the workspace a patch table (cdv_graph_build_table)?
-bool cdv_graph_is_table(const void* ws);
-// ... and its capacity in slots (0: not a table)
-int64_t cdv_graph_table_capacity(const void* ws);
 
 // is the index a usable one: the error state of the ranked build, or of the table build (a negative id, two ids in one
 // slot, a patch with more edges than the sort launch serves)

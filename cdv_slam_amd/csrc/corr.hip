@@ -859,9 +859,7 @@ int corr_fused_impl(const FusedCall& c) {
               CDV_ERR_UNSUPPORTED, "cdv_corr_fused: a feature ring of 4 GB or more");
   CDV_REQUIRE(c.kmod >= 0 && c.jmod >= 0 && c.kmod < ((int64_t)1 << 31) && c.jmod < ((int64_t)1 << 31), CDV_ERR_ARG,
               "cdv_corr_fused: kmod / jmod out of range");
-  // ceil(2^32 / d): mulhi(x, magic) is x / d or x / d + 1 for 0 <= x < 2^31
-  const uint32_t kmagic = c.kmod > 1 ? (uint32_t)((((uint64_t)1 << 32) + (uint64_t)c.kmod - 1) / (uint64_t)c.kmod) : 0u;
-  const uint32_t jmagic = c.jmod > 1 ? (uint32_t)((((uint64_t)1 << 32) + (uint64_t)c.jmod - 1) / (uint64_t)c.jmod) : 0u;
+  const uint32_t kmagic = cdv_magic_u32(c.kmod), jmagic = cdv_magic_u32(c.jmod);
   if (c.E == 0) return CDV_OK;
   CDV_REQUIRE(nlev == 1 || ex1 >= ex0, CDV_ERR_UNSUPPORTED, "cdv_corr_fused: level 1 must not be finer than level 0");
   static const int exp = getenv("CDV_CORR_EXP") ? atoi(getenv("CDV_CORR_EXP")) : 0;  // diagnostics only

@@ -25,7 +25,6 @@
 //                predecessor / successor in time (fastba.neighbors); clears the fill cursors
 #include <mutex>
 #include <unordered_map>
-#include <unordered_set>
 #include <vector>
 
 #include "cdv_common.h"
@@ -38,17 +37,26 @@ CDV_STAMP_TU(graph)
 
 namespace {
 
+// What the library knows about the index in a workspace, by workspace ADDRESS.  Who sets a field and what clears it:
+//   L, initialised          set by cdv_graph_workspace_init and by every build (its prepare half).  An entry that only
+//                           cdv_graph_bind_corr_stream or cdv_graph_no_corr_order made has initialised == false: it holds
+//                           no index, and cdv_graph_info says so
+//   has_ii, table, tab_cap  the form of the LAST build: rewritten by every build (has_ii of a ranked build by its finish
+//                           half, which is the one given ii), cleared by cdv_graph_workspace_init
+//   cs                      set by cdv_graph_bind_corr_stream, survives builds, dropped by cdv_graph_workspace_init
+//   no_order                set by cdv_graph_no_corr_order, survives builds and cdv_graph_workspace_init
+// cdv_graph_forget erases the entry and with it every field.
 struct RegEntry {
-  GraphLayout L;
-  bool initialised;
-  bool has_ii;
-  CorrStream cs;      // coords == nullptr: no packed correlation stream is written
-  bool table;         // the index in the workspace is a patch table
-  int32_t tab_cap;    // ... of this capacity (slots)
+  GraphLayout L{};
+  bool initialised = false;
+  bool has_ii = false;
+  CorrStream cs = CORR_STREAM_NONE;   // coords == nullptr: no packed correlation stream is written
+  bool table = false;                 // the index in the workspace is a patch table
+  int32_t tab_cap = 0;                // ... of this capacity (slots)
+  bool no_order = false;              // builds skip the correlation's processing order
 };
 std::mutex g_reg_mutex;
 std::unordered_map<const void*, RegEntry> g_registry;
-std::unordered_set<const void*> g_no_order;   // workspaces whose builds skip the correlation's processing order (cdv_graph_no_corr_order)
 
 
 __global__ __launch_bounds__(256) void graph_init_kernel(int32_t* meta, int32_t* khist, int32_t* kcursor, int32_t* tcur,
@@ -797,27 +805,41 @@ inline int grid_for(int64_t n, int threads, int cap) {
   return b < cap ? b : cap;
 }
 
-}  // namespace
-
-bool cdv_graph_lookup(const void* ws, GraphLayout* out) {
-  std::lock_guard<std::mutex> lk(g_reg_mutex);
-  auto it = g_registry.find(ws);
-  if (it == g_registry.end()) return false;
-  *out = it->second.L;
-  return true;
+void launch_init(const GraphView& v, int64_t k_range, void* stream) {
+  hipLaunchKernelGGL(graph_init_kernel, dim3(grid_for(k_range + 1 + GM_WORDS, 256, 2048)), dim3(256), 0, (hipStream_t)stream,
+                     v.meta, v.khist, v.kcursor, v.tcur, v.town, k_range);
 }
 
-bool cdv_graph_has_ii(const void* ws) {
+// The registry half of a build's prepare step: records the layout and the form of the index about to be built (a bound
+// stream and the no-order flag stay) and, when the library has not initialised this address for this layout, zeroes what the
+// builds keep zero between calls.
+void register_build(void* ws, const GraphLayout& L, const GraphView& v, bool has_ii, bool table, int32_t tab_cap, void* stream) {
+  bool need_init;
+  {
+    std::lock_guard<std::mutex> lk(g_reg_mutex);
+    RegEntry& e = g_registry[ws];
+    need_init = !e.initialised || e.L.E_max != L.E_max || e.L.k_range != L.k_range;
+    e.L = L; e.initialised = true;
+    e.has_ii = has_ii; e.table = table; e.tab_cap = tab_cap;
+  }
+  if (need_init) launch_init(v, L.k_range, stream);
+}
+
+}  // namespace
+
+bool cdv_graph_info(const void* ws, GraphInfo* out) {
   std::lock_guard<std::mutex> lk(g_reg_mutex);
   auto it = g_registry.find(ws);
-  return it != g_registry.end() && it->second.has_ii;
+  if (it == g_registry.end() || !it->second.initialised) return false;
+  const RegEntry& e = it->second;
+  out->L = e.L; out->has_ii = e.has_ii; out->table = e.table; out->tab_cap = e.table ? e.tab_cap : 0;
+  return true;
 }
 
 // forget what is known about a workspace address (see cdv_workspace_forget in the header)
 void cdv_graph_forget(const void* ws) {
   std::lock_guard<std::mutex> lk(g_reg_mutex);
   g_registry.erase(ws);
-  g_no_order.erase(ws);
 }
 
 // Explicit initialisation of an index workspace: zeroes what the builds keep zero between calls (histogram, cursors,
@@ -830,12 +852,13 @@ extern "C" int cdv_graph_workspace_init(void* ws, size_t ws_bytes, int64_t E_max
   CDV_REQUIRE(k_range >= 1 && k_range < ((int64_t)1 << 31) - 64 && E_max >= 1, CDV_ERR_ARG, "cdv_graph_workspace_init: bad sizes");
   const GraphLayout L = graph_layout(E_max, k_range);
   CDV_REQUIRE(L.total <= ws_bytes, CDV_ERR_WORKSPACE, "cdv_graph_workspace_init: workspace too small for (E_max, k_range)");
-  const GraphView v = graph_view(ws, L);
-  hipLaunchKernelGGL(graph_init_kernel, dim3(grid_for(k_range + 1 + GM_WORDS, 256, 2048)), dim3(256), 0, (hipStream_t)stream,
-                     v.meta, v.khist, v.kcursor, v.tcur, v.town, k_range);
+  launch_init(graph_view(ws, L), k_range, stream);
   CDV_LAUNCH_CHECK();
   std::lock_guard<std::mutex> lk(g_reg_mutex);
-  g_registry[ws] = RegEntry{L, true, false, CorrStream{nullptr, 0, 0, 0, 0, 0, 0, 1.0f}, false, 0};
+  RegEntry& e = g_registry[ws];
+  e.L = L; e.initialised = true;
+  e.has_ii = false; e.table = false; e.tab_cap = 0;
+  e.cs = CORR_STREAM_NONE;
   return CDV_OK;
 }
 
@@ -864,19 +887,8 @@ int cdv_graph_prepare(const int64_t* jj, const int64_t* kk, int64_t E, void* ws,
               "cdv_graph_build: need 1 <= E <= E_max, k_range >= 1");
   const GraphLayout L = graph_layout(E_max, k_range);
   CDV_REQUIRE(L.total <= ws_bytes, CDV_ERR_WORKSPACE, "cdv_graph_build: workspace too small for (E_max, k_range)");
-  bool need_init;
-  {
-    std::lock_guard<std::mutex> lk(g_reg_mutex);
-    auto it = g_registry.find(ws);
-    need_init = it == g_registry.end() || !it->second.initialised || it->second.L.E_max != E_max ||
-                it->second.L.k_range != k_range;
-    const CorrStream keep = it != g_registry.end() ? it->second.cs : CorrStream{nullptr, 0, 0, 0, 0, 0, 0, 1.0f};
-    g_registry[ws] = RegEntry{L, true, false, keep, false, 0};
-  }
   const GraphView v = graph_view(ws, L);
-  if (need_init)
-    hipLaunchKernelGGL(graph_init_kernel, dim3(grid_for(k_range + 1 + GM_WORDS, 256, 2048)), dim3(256), 0,
-                       (hipStream_t)stream, v.meta, v.khist, v.kcursor, v.tcur, v.town, k_range);
+  register_build(ws, L, v, false, false, 0, stream);   // (has_ii: cdv_graph_finish is the half that is given ii)
   *hist = cdv::HistArgs{jj, kk, (int32_t)E, v.stage, v.khist, (int32_t)k_range, v.meta, v.kcount, v.krank, v.ocnt};
   *hist_blocks = E > 0 ? grid_for(E, 256, GRAPH_MAX_BLOCKS) : 0;
   return CDV_OK;
@@ -886,7 +898,7 @@ int cdv_graph_finish(const int64_t* ii, const int64_t* jj, const int64_t* kk, in
                      int64_t k_range, int hist_blocks, int64_t* ix, int64_t* jx, void* stream) {
   const GraphLayout L = graph_layout(E_max, k_range);
   const GraphView v = graph_view(ws, L);
-  CorrStream cs{nullptr, 0, 0, 0, 0, 0, 0, 1.0f};
+  CorrStream cs = CORR_STREAM_NONE;
   bool want_order = true;
   {
     std::lock_guard<std::mutex> lk(g_reg_mutex);
@@ -894,8 +906,8 @@ int cdv_graph_finish(const int64_t* ii, const int64_t* jj, const int64_t* kk, in
     if (it != g_registry.end()) {
       it->second.has_ii = ii != nullptr && E > 0;
       cs = it->second.cs;
+      want_order = !it->second.no_order;
     }
-    want_order = g_no_order.find(ws) == g_no_order.end();
   }
   hipStream_t s = (hipStream_t)stream;
   const int32_t En = (int32_t)E;
@@ -919,24 +931,12 @@ int cdv_graph_finish(const int64_t* ii, const int64_t* jj, const int64_t* kk, in
   return CDV_OK;
 }
 
-// An index that no correlation will ever walk (the frame-pair index of a global bundle adjustment: ba.hip): its builds skip the
+// An index that no correlation will ever walk (the frame-pair index of a global bundle adjustment: ba_big.hip): its builds skip the
 // correlation's processing order -- every workgroup of the fill launch sums the whole per-block count table for it, which is
 // nothing at the ~190 blocks of a frame-to-frame graph and 130 MB of reads at the 1024 blocks of a 700 k-edge one.
 void cdv_graph_no_corr_order(const void* ws) {
   std::lock_guard<std::mutex> lk(g_reg_mutex);
-  g_no_order.insert(ws);
-}
-
-bool cdv_graph_is_table(const void* ws) {
-  std::lock_guard<std::mutex> lk(g_reg_mutex);
-  auto it = g_registry.find(ws);
-  return it != g_registry.end() && it->second.table;
-}
-
-int64_t cdv_graph_table_capacity(const void* ws) {
-  std::lock_guard<std::mutex> lk(g_reg_mutex);
-  auto it = g_registry.find(ws);
-  return (it != g_registry.end() && it->second.table) ? it->second.tab_cap : 0;
+  g_registry[ws].no_order = true;
 }
 
 // The table build in two halves (like cdv_graph_prepare / cdv_graph_finish), so that cdv_update_prologue_table can run the
@@ -955,19 +955,8 @@ int cdv_graph_table_prepare(const int64_t* ii, const int64_t* jj, const int64_t*
               "cdv_graph_build_table: table capacity must lie in [1, min(k_range, 65536)]");
   const GraphLayout L = graph_layout(E_max, k_range);
   CDV_REQUIRE(L.total <= ws_bytes, CDV_ERR_WORKSPACE, "cdv_graph_build_table: workspace too small for (E_max, k_range)");
-  bool need_init;
-  {
-    std::lock_guard<std::mutex> lk(g_reg_mutex);
-    auto it = g_registry.find(ws);
-    need_init = it == g_registry.end() || !it->second.initialised || it->second.L.E_max != E_max ||
-                it->second.L.k_range != k_range;
-    const CorrStream keep = it != g_registry.end() ? it->second.cs : CorrStream{nullptr, 0, 0, 0, 0, 0, 0, 1.0f};
-    g_registry[ws] = RegEntry{L, true, ii != nullptr && E > 0, keep, true, (int32_t)tab_cap};
-  }
   const GraphView v = graph_view(ws, L);
-  if (need_init)
-    hipLaunchKernelGGL(graph_init_kernel, dim3(grid_for(k_range + 1 + GM_WORDS, 256, 2048)), dim3(256), 0,
-                       (hipStream_t)stream, v.meta, v.khist, v.kcursor, v.tcur, v.town, k_range);
+  register_build(ws, L, v, ii != nullptr && E > 0, true, (int32_t)tab_cap, stream);
   // (the build's generation is a device word, GM_GENNEXT: nothing of this call's host state reaches the launches by value
   // except sizes and pointers, so the two launches may be captured into a hipGraph and replayed any number of times)
   *fill = cdv::TFillArgs{ii, jj, kk, (int32_t)E, (int32_t)tab_cap, v.meta, v.tcur, v.town, v.ttab, v.tovf, v.tprec, v.ocnt, dyn};
@@ -980,7 +969,7 @@ int cdv_graph_table_finish(const cdv::TFillArgs& fill, int fill_blocks, void* ws
                            bool with_stream, void* stream) {
   const GraphLayout L = graph_layout(E_max, k_range);
   const GraphView v = graph_view(ws, L);
-  CorrStream cs{nullptr, 0, 0, 0, 0, 0, 0, 1.0f};
+  CorrStream cs = CORR_STREAM_NONE;
   {
     std::lock_guard<std::mutex> lk(g_reg_mutex);
     auto it = g_registry.find(ws);
@@ -1039,9 +1028,9 @@ extern "C" int cdv_graph_build_edges(const int64_t* ii, const int64_t* jj, const
 }
 
 extern "C" const int32_t* cdv_graph_corr_order(const void* ws) {
-  GraphLayout L;
-  if (!cdv_graph_lookup(ws, &L)) return nullptr;
-  return graph_view((void*)ws, L).order;
+  GraphInfo gi;
+  if (!cdv_graph_info(ws, &gi)) return nullptr;
+  return graph_view((void*)ws, gi.L).order;
 }
 
 extern "C" int cdv_graph_bind_corr_stream(void* ws, const float* coords, int64_t kmod, int64_t jmod, int64_t Ng,
@@ -1052,31 +1041,34 @@ extern "C" int cdv_graph_bind_corr_stream(void* ws, const float* coords, int64_t
   CDV_REQUIRE(kmod >= 0 && jmod >= 0 && kmod < ((int64_t)1 << 31) && jmod < ((int64_t)1 << 31) && Ng >= 0 &&
                   Ng < ((int64_t)1 << 31) && slots >= 0 && slots < ((int64_t)1 << 31),
               CDV_ERR_ARG, "cdv_graph_bind_corr_stream: moduli / ring sizes out of range");
-  CorrStream cs{coords, (uint32_t)kmod, (uint32_t)jmod, 0u, 0u, (uint32_t)Ng, (uint32_t)slots, 1.0f / scale0};
-  cs.kmagic = kmod > 1 ? (uint32_t)((((uint64_t)1 << 32) + (uint64_t)kmod - 1) / (uint64_t)kmod) : 0u;
-  cs.jmagic = jmod > 1 ? (uint32_t)((((uint64_t)1 << 32) + (uint64_t)jmod - 1) / (uint64_t)jmod) : 0u;
+  CorrStream cs = CORR_STREAM_NONE;
+  cs.coords = coords;
+  cs.kmod = (uint32_t)kmod; cs.kmagic = cdv_magic_u32(kmod);
+  cs.jmod = (uint32_t)jmod; cs.jmagic = cdv_magic_u32(jmod);
+  cs.Ng = (uint32_t)Ng;
+  cs.slots = (uint32_t)slots;
+  cs.inv_scale0 = 1.0f / scale0;
   std::lock_guard<std::mutex> lk(g_reg_mutex);
-  auto it = g_registry.find(ws);
-  if (it == g_registry.end()) g_registry[ws] = RegEntry{GraphLayout{}, false, false, cs, false, 0};
-  else it->second.cs = cs;
+  g_registry[ws].cs = cs;   // (an address the library has not seen: an entry without an index, see RegEntry)
   return CDV_OK;
 }
 
 extern "C" const uint32_t* cdv_graph_corr_records(const void* ws) {
-  GraphLayout L;
-  if (!cdv_graph_lookup(ws, &L)) return nullptr;
-  return graph_view((void*)ws, L).crec;
+  GraphInfo gi;
+  if (!cdv_graph_info(ws, &gi)) return nullptr;
+  return graph_view((void*)ws, gi.L).crec;
 }
 
 extern "C" int cdv_graph_read_meta_host(const void* ws, int64_t* meta_host, void* stream) {
-  GraphLayout L;
-  CDV_REQUIRE(cdv_graph_lookup(ws, &L), CDV_ERR_ARG, "cdv_graph_read_meta_host: workspace has no built graph");
+  GraphInfo gi;
+  CDV_REQUIRE(cdv_graph_info(ws, &gi), CDV_ERR_ARG, "cdv_graph_read_meta_host: workspace has no built graph");
+  const GraphLayout& L = gi.L;
   int32_t m[GM_WORDS];
   CDV_HIP_CHECK(hipMemcpyAsync(m, (const char*)ws + L.meta, sizeof(m), hipMemcpyDeviceToHost, (hipStream_t)stream));
   CDV_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
-  if (cdv_graph_is_table(ws)) {   // patch table: live patches and their id range from the per-slot ids; no frame range is kept
+  if (gi.table) {   // patch table: live patches and their id range from the per-slot ids; no frame range is kept
     const int err = m[GM_TERR + (m[GM_GEN] & 1)] != 0;
-    const int cap = (int)cdv_graph_table_capacity(ws);
+    const int cap = (int)gi.tab_cap;
     std::vector<int32_t> kid((size_t)(cap > 0 ? cap : 0));
     if (cap > 0) {
       CDV_HIP_CHECK(hipMemcpyAsync(kid.data(), (const char*)ws + L.tkid, sizeof(int32_t) * (size_t)cap, hipMemcpyDeviceToHost,
@@ -1097,12 +1089,12 @@ extern "C" int cdv_graph_read_meta_host(const void* ws, int64_t* meta_host, void
 
 extern "C" int cdv_graph_get_unique(const void* ws, int64_t* kx, int64_t kx_capacity, int64_t* ku, int64_t E,
                                     void* stream) {
-  GraphLayout L;
-  CDV_REQUIRE(cdv_graph_lookup(ws, &L), CDV_ERR_ARG, "cdv_graph_get_unique: workspace has no built graph");
-  CDV_REQUIRE(!cdv_graph_is_table(ws), CDV_ERR_UNSUPPORTED,
+  GraphInfo gi;
+  CDV_REQUIRE(cdv_graph_info(ws, &gi), CDV_ERR_ARG, "cdv_graph_get_unique: workspace has no built graph");
+  CDV_REQUIRE(!gi.table, CDV_ERR_UNSUPPORTED,
               "cdv_graph_get_unique: the workspace holds a patch table (no ranks); build the ranked index (cdv_graph_build*)");
   if (E == 0) return CDV_OK;
-  const GraphView v = graph_view((void*)ws, L);
+  const GraphView v = graph_view((void*)ws, gi.L);
   const int64_t n = E > kx_capacity ? E : kx_capacity;
   hipLaunchKernelGGL(graph_copy_unique_kernel, dim3(grid_for(n, 256, 1024)), dim3(256), 0, (hipStream_t)stream, v.meta,
                      v.kx, v.ku, kx, kx_capacity, ku, (int32_t)E);
@@ -1111,10 +1103,10 @@ extern "C" int cdv_graph_get_unique(const void* ws, int64_t* kx, int64_t kx_capa
 }
 
 extern "C" int cdv_neighbors(const void* ws, int64_t E, int64_t* ix, int64_t* jx, void* stream) {
-  GraphLayout L;
-  CDV_REQUIRE(cdv_graph_lookup(ws, &L), CDV_ERR_ARG, "cdv_neighbors: workspace has no built graph");
+  GraphInfo gi;
+  CDV_REQUIRE(cdv_graph_info(ws, &gi), CDV_ERR_ARG, "cdv_neighbors: workspace has no built graph");
   if (E == 0) return CDV_OK;
-  const GraphView v = graph_view((void*)ws, L);
+  const GraphView v = graph_view((void*)ws, gi.L);
   hipLaunchKernelGGL(graph_neighbors_kernel, dim3(grid_for(E, 256, 1024)), dim3(256), 0, (hipStream_t)stream,
                      (int32_t)E, v.meta, v.nprev, v.nnext, ix, jx);
   CDV_LAUNCH_CHECK();
