@@ -223,7 +223,8 @@ __device__ __forceinline__ void lt_so3_log(const T* qd, T* phi) {  // so3.h:115-
     T n = t_sqrt<T>(sq);
     T aw = w < 0 ? -w : w;
     if (aw < CDV_LIE_EPS) {
-      f = (w > 0) ? T(3.14159265358979323846) / n : -T(3.14159265358979323846) / n;
+      // 2 atan(n / w) = +-pi - 2 atan(w / n).  so3.h stops at +-pi / n here, which is 2 |w| off: 1.8e-6 rad at |w| = 9e-7
+      f = ((w > 0 ? T(3.14159265358979323846) : -T(3.14159265358979323846)) - T(2) * t_atan<T>(w / n)) / n;
     } else {
       f = T(2) * t_atan<T>(n / w) / n;
     }
@@ -243,7 +244,11 @@ __device__ __forceinline__ void lt_so3_left_jacobian(const T* phi, T* J) {  // s
     c1 = T(1.0 / 2.0) - T(1.0 / 24.0) * theta2;
     c2 = T(1.0 / 6.0) - T(1.0 / 120.0) * theta2;
   } else {
-    c1 = (T)((1.0 - t_cos<T>(theta)) / theta2);
+    // c1 = (1 - cos theta) / theta^2 as 2 sin^2(theta / 2) / theta^2: so3.h's 1 - cos theta turns the rounding of
+    // cos theta into u / theta^2 of c1, i.e. (u / theta) |tau| of the translation -- 4e-4 |tau| in float32 at the
+    // angles of a BA increment.  c2's cancellation is multiplied by theta^2 and costs u |tau| only.
+    const T sh = t_sin<T>(T(0.5) * theta);
+    c1 = T(2) * sh * sh / theta2;
     c2 = (T)((theta - t_sin<T>(theta)) / (theta2 * theta));
   }
 #pragma unroll

@@ -106,7 +106,11 @@ static inline void SUF(so3_log)(const REAL *qd, REAL *phi) {
     REAL n = (sizeof(REAL) == 4) ? (REAL)sqrtf((float)sq) : (REAL)sqrt((double)sq);
     REAL aw = w < 0 ? -w : w;
     if (aw < LIE_EPS) {
-      f = (w > 0) ? (REAL)LIE_PI / n : -(REAL)LIE_PI / n;
+      /* DEPARTS from so3.h:139-143, which returns +-pi / n here: that is 2 |w| off (1.8e-6 rad at |w| = 9e-7, in
+       * either precision), and this file is the yardstick of the kernels.  2 atan(n / w) = +-pi - 2 atan(w / n).
+       * The reference's value is kept on record by tests/test_lie_truth_cpu.py (variant `reference_pi_branch`). */
+      REAL at = (sizeof(REAL) == 4) ? (REAL)atanf((float)(w / n)) : (REAL)atan((double)(w / n));
+      f = ((w > 0 ? (REAL)LIE_PI : -(REAL)LIE_PI) - (REAL)2 * at) / n;
     } else {
       REAL at = (sizeof(REAL) == 4) ? (REAL)atanf((float)(n / w)) : (REAL)atan((double)(n / w));
       f = (REAL)2 * at / n;
