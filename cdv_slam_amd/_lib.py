@@ -76,6 +76,7 @@ SIGNATURES = {
     "cdv_ba_factor_ticket": (_i32, [_i32, _i32, _vp]),
     "cdv_ba_set_patches_per_frame": (_i32, [_vp, _i32]),
     "cdv_lie_op": (_i32, [_i32, _i32, _i32, _i64, _vp, _vp, _vp, _vp]),
+    "cdv_lie_bwd": (_i32, [_vp, _vp]),
     # ---- a frame stream whose sizes live on the device
     "cdv_update_prologue_table_dyn": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i64, _i64, _vp, _vp, _vp,
                                              _vp, _vp, _vp, _i64, _vp, _vp, _vp, _sz, _i64, _i64, _i64, _vp]),
@@ -121,6 +122,13 @@ def _stream_desc_fields():
 class StreamDesc(ctypes.Structure):
     """cdv_stream_desc (include/cdvslam_hip.h): the buffers and sizes of a device-resident frame stream, field for field"""
     _fields_ = _stream_desc_fields()
+
+
+class LieBwdArgs(ctypes.Structure):
+    """cdv_lie_bwd_args (include/cdvslam_hip.h): one backward call of a Lie op, field for field"""
+    _fields_ = ([(n, ctypes.c_int32) for n in ("group", "op", "dtype", "need")]
+                + [(n, ctypes.c_int64) for n in ("n", "rep_x", "rep_y")]
+                + [(n, ctypes.c_void_p) for n in ("grad", "x", "y", "dx", "dy")])
 
 
 class ShadowRing(ctypes.Structure):

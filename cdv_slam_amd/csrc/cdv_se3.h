@@ -290,6 +290,119 @@ __device__ __forceinline__ void lt_se3_log(const T* X, T* xi) {  // se3.h:124-13
   xi[3] = phi[0]; xi[4] = phi[1]; xi[5] = phi[2];
 }
 
+// ---- what the backward adds (lie_bwd.hip): ad(), and the SE3 left Jacobian and its inverse in blocks -------------
+// Tangents are (tau, phi).  Jl(xi) = [[J, Q], [0, J]] and Jl^-1(xi) = [[J^-1, -J^-1 Q J^-1], [0, J^-1]] with J the SO3 left
+// Jacobian of phi and Q(tau, phi) the coupling block (Barfoot, State Estimation for Robotics, eq. 7.86):
+//   Q = T/2 + ca (PT + TP + PTP) + cb (PPT + TPP - 3 PTP) + cc (PTPP + PPTP),       T = [tau]x, P = [phi]x
+//   ca = (th - sin th) / th^3,  cb = (th^2 + 2 cos th - 2) / (2 th^4),  cc = (2 th - 3 sin th + th cos th) / (2 th^5)
+
+// row . ad(b) for SO3 is (row x b); the backward of Ad(X) a wants -row . ad(b):
+//   SO3: b x row            SE3, b = (tau, phi), row = (u, w): (phi x u, tau x u + phi x w)
+template <typename T, bool SE3>
+__device__ __forceinline__ void lt_neg_row_times_ad(const T* row, const T* b, T* o) {
+  if constexpr (SE3) {
+    T a[3], c[3], d[3];
+    cross3(b + 3, row, a);
+    cross3(b, row, c);
+    cross3(b + 3, row + 3, d);
+    o[0] = a[0]; o[1] = a[1]; o[2] = a[2];
+    o[3] = c[0] + d[0]; o[4] = c[1] + d[1]; o[5] = c[2] + d[2];
+  } else {
+    cross3(b, row, o);
+  }
+}
+
+// ca, cb, cc above.  The closed forms subtract nearly equal numbers: their absolute error is u th / th^3, 2 u / th^4 and
+// 3 u th / th^5, which reaches the block as (u / th) |tau| -- a thousand roundings at th = 1e-3, far above the 1e-6 switch of
+// the other series here.  So: the power series in th^2 below 1 rad (terms fall by th^2 / 42 at the least; the last kept is
+// below u / 8 of the first), the closed forms above, where they cost at most 2 u |tau|.
+template <typename T>
+__device__ __forceinline__ void lt_q_coeffs(T theta2, T& ca, T& cb, T& cc) {
+  if (theta2 < T(1)) {
+    constexpr int NT = sizeof(T) == 4 ? 6 : 10;
+    // 1 / (2k + 3)!, 1 / (2k + 4)!, (k + 1) / (2k + 5)!, signs alternating
+    constexpr double A[10] = {1.0 / 6, -1.0 / 120, 1.0 / 5040, -1.0 / 362880, 1.0 / 39916800, -1.0 / 6227020800.0,
+                              1.0 / 1307674368000.0, -1.0 / 355687428096000.0, 1.0 / 121645100408832000.0,
+                              -1.0 / 51090942171709440000.0};
+    constexpr double B[10] = {1.0 / 24, -1.0 / 720, 1.0 / 40320, -1.0 / 3628800, 1.0 / 479001600, -1.0 / 87178291200.0,
+                              1.0 / 20922789888000.0, -1.0 / 6402373705728000.0, 1.0 / 2432902008176640000.0,
+                              -1.0 / 1124000727777607680000.0};
+    constexpr double C[10] = {1.0 / 120, -2.0 / 5040, 3.0 / 362880, -4.0 / 39916800, 5.0 / 6227020800.0,
+                              -6.0 / 1307674368000.0, 7.0 / 355687428096000.0, -8.0 / 121645100408832000.0,
+                              9.0 / 51090942171709440000.0, -10.0 / 25852016738884976640000.0};
+    ca = T(A[NT - 1]); cb = T(B[NT - 1]); cc = T(C[NT - 1]);
+#pragma unroll
+    for (int k = NT - 2; k >= 0; k--) {
+      ca = ca * theta2 + T(A[k]);
+      cb = cb * theta2 + T(B[k]);
+      cc = cc * theta2 + T(C[k]);
+    }
+  } else {
+    const T theta = t_sqrt<T>(theta2), s = t_sin<T>(theta), c = t_cos<T>(theta), sh = t_sin<T>(T(0.5) * theta);
+    const T theta4 = theta2 * theta2;
+    ca = (theta - s) / (theta2 * theta);
+    cb = (T(0.5) * theta2 - T(2) * sh * sh) / theta4;        // 1 - cos th as 2 sin^2(th / 2), as in the SO3 Jacobian
+    cc = (T(2) * theta - T(3) * s + theta * c) / (T(2) * theta4 * theta);
+  }
+}
+
+template <typename T>
+__device__ __forceinline__ void lt_se3_Q(const T* tau, const T* phi, T* Q) {
+  T Tm[9], P[9], PT[9], TP[9], PTP[9], PPT[9], TPP[9], PTPP[9], PPTP[9];
+  hat3(tau, Tm);
+  hat3(phi, P);
+  mat3_mul(P, Tm, PT);
+  mat3_mul(Tm, P, TP);
+  mat3_mul(PT, P, PTP);
+  mat3_mul(P, PT, PPT);
+  mat3_mul(TP, P, TPP);
+  mat3_mul(PTP, P, PTPP);
+  mat3_mul(P, PTP, PPTP);
+  T ca, cb, cc;
+  lt_q_coeffs<T>(phi[0] * phi[0] + phi[1] * phi[1] + phi[2] * phi[2], ca, cb, cc);
+#pragma unroll
+  for (int i = 0; i < 9; i++)
+    Q[i] = T(0.5) * Tm[i] + ca * (PT[i] + TP[i] + PTP[i]) + cb * (PPT[i] + TPP[i] - T(3) * PTP[i]) + cc * (PTPP[i] + PPTP[i]);
+}
+
+// row . Jl(xi):  (u, w) -> (J^T u, Q^T u + J^T w)
+template <typename T>
+__device__ __forceinline__ void lt_se3_row_times_left_jacobian(const T* xi, const T* row, T* o) {
+  T J[9], Q[9], a[3], b[3];
+  lt_so3_left_jacobian(xi + 3, J);
+  lt_se3_Q(xi, xi + 3, Q);
+  mat3T_vec(J, row, o);
+  mat3T_vec(Q, row, a);
+  mat3T_vec(J, row + 3, b);
+  o[3] = a[0] + b[0]; o[4] = a[1] + b[1]; o[5] = a[2] + b[2];
+}
+
+// row . Jl^-1(xi):  (u, w) -> (s, J^-T (w - Q^T s)),  s = J^-T u
+template <typename T>
+__device__ __forceinline__ void lt_se3_row_times_left_jacobian_inverse(const T* xi, const T* row, T* o) {
+  T Ji[9], Q[9], s[3], a[3];
+  lt_so3_left_jacobian_inverse(xi + 3, Ji);
+  lt_se3_Q(xi, xi + 3, Q);
+  mat3T_vec(Ji, row, s);
+  mat3T_vec(Q, s, a);
+  a[0] = row[3] - a[0]; a[1] = row[4] - a[1]; a[2] = row[5] - a[2];
+  o[0] = s[0]; o[1] = s[1]; o[2] = s[2];
+  mat3T_vec(Ji, a, o + 3);
+}
+
+// Jl^-1(xi) . a:  (a1, a2) -> (J^-1 (a1 - Q r), r),  r = J^-1 a2
+template <typename T>
+__device__ __forceinline__ void lt_se3_left_jacobian_inverse_times(const T* xi, const T* a, T* o) {
+  T Ji[9], Q[9], r[3], b[3];
+  lt_so3_left_jacobian_inverse(xi + 3, Ji);
+  lt_se3_Q(xi, xi + 3, Q);
+  mat3_vec(Ji, a + 3, r);
+  mat3_vec(Q, r, b);
+  b[0] = a[0] - b[0]; b[1] = a[1] - b[1]; b[2] = a[2] - b[2];
+  mat3_vec(Ji, b, o);
+  o[3] = r[0]; o[4] = r[1]; o[5] = r[2];
+}
+
 // ---- fastba semantics, on the primitives above (float only) -----------------------------------------------
 // fastba differs from lietorch in conventions, not in geometry: group elements are used as
 // stored -- NO quaternion re-normalisation anywhere (ba_cuda.cu:74-85 vs so3.h:30-37) -- the exponential switches to

@@ -1,4 +1,5 @@
-// lie.hip -- batched SO3 / SE3 forward ops (lietorch_backends replacement), gfx950.
+// lie.hip -- batched SO3 / SE3 forward ops (lietorch_backends replacement), gfx950; `projector` and `Jinv`, which the
+// backward's callers use and which have the forward's shape (x, optional y -> z), are ops 9 and 10 here.
 //
 // One lane per batch element, fixed-size math in registers (cdv_se3.h restates
 // cdvslam/lietorch/include/so3.h, se3.h).  Reference kernels: lietorch/src/lietorch_gpu.cu:25-299.
@@ -7,7 +8,7 @@
 
 namespace {
 
-enum { OP_EXP = 0, OP_LOG, OP_INV, OP_MUL, OP_ADJ, OP_ADJT, OP_ACT, OP_ACT4, OP_MATRIX };
+enum { OP_EXP = 0, OP_LOG, OP_INV, OP_MUL, OP_ADJ, OP_ADJT, OP_ACT, OP_ACT4, OP_MATRIX, OP_PROJECTOR, OP_JINV };
 
 template <typename T, bool SE3, int OP>
 __global__ __launch_bounds__(256) void lie_kernel(int64_t n, const T* __restrict__ x, const T* __restrict__ y,
@@ -100,6 +101,47 @@ __global__ __launch_bounds__(256) void lie_kernel(int64_t n, const T* __restrict
       M[4 * a + 3] = t[a];
     }
     M[12] = 0; M[13] = 0; M[14] = 0; M[15] = 1;
+  } else if constexpr (OP == OP_PROJECTOR) {
+    // [N][N]: column k < K is d (stored row of Exp(eps) X) / d eps_k at eps = 0; the last column is zero.
+    //   t' = t + tau + phi x t,   (v, w)' = (v, w) + (w phi + phi x v, -phi . v) / 2
+    T X[N], t[3] = {0, 0, 0}, q[4], Tx[9], Vx[9];
+#pragma unroll
+    for (int c = 0; c < N; c++) X[c] = x[N * i + c];
+    if constexpr (SE3) cdv::lt_se3_load(X, t, q); else cdv::lt_quat_load(X, q);
+    cdv::hat3(t, Tx);
+    cdv::hat3(q, Vx);
+    T* M = z + N * N * i;
+    constexpr int R0 = SE3 ? 3 : 0;            // first row and column of the rotation part
+#pragma unroll
+    for (int a = 0; a < N; a++)
+#pragma unroll
+      for (int b = 0; b < N; b++) {
+        T v = T(0);
+        if (SE3 && a < 3 && b < 3) v = (a == b) ? T(1) : T(0);
+        else if (SE3 && a < 3 && b < 6) v = -Tx[3 * a + (b - 3)];
+        else if (a >= R0 && a < R0 + 3 && b >= R0 && b < R0 + 3)
+          v = T(0.5) * (((a == b) ? q[3] : T(0)) - Vx[3 * (a - R0) + (b - R0)]);
+        else if (a == N - 1 && b >= R0 && b < R0 + 3) v = T(-0.5) * q[b - R0];
+        M[N * a + b] = v;
+      }
+  } else if constexpr (OP == OP_JINV) {
+    // Jl^-1(Log X) a
+    T X[N], a[K], xi[K], o[K];
+#pragma unroll
+    for (int c = 0; c < N; c++) X[c] = x[N * i + c];
+#pragma unroll
+    for (int c = 0; c < K; c++) a[c] = y[K * i + c];
+    if constexpr (SE3) {
+      cdv::lt_se3_log(X, xi);
+      cdv::lt_se3_left_jacobian_inverse_times(xi, a, o);
+    } else {
+      T Ji[9];
+      cdv::lt_so3_log(X, xi);
+      cdv::lt_so3_left_jacobian_inverse(xi, Ji);
+      cdv::mat3_vec(Ji, a, o);
+    }
+#pragma unroll
+    for (int c = 0; c < K; c++) z[K * i + c] = o[c];
   }
 }
 
@@ -121,6 +163,8 @@ int launch_op(int op, int64_t n, const T* x, const T* y, T* z, hipStream_t s) {
     CDV_LIE_CASE(OP_ACT)
     CDV_LIE_CASE(OP_ACT4)
     CDV_LIE_CASE(OP_MATRIX)
+    CDV_LIE_CASE(OP_PROJECTOR)
+    CDV_LIE_CASE(OP_JINV)
     default:
       cdv_set_error(CDV_ERR_ARG, "cdv_lie_op: unknown op");
       return CDV_ERR_ARG;
@@ -137,7 +181,7 @@ extern "C" int cdv_lie_op(int group, int op, int dtype, int64_t n, const void* x
   CDV_REQUIRE(group == 1 || group == 3, CDV_ERR_UNSUPPORTED,
               "cdv_lie_op: only SO3 (1) and SE3 (3) are on the update path; RxSO3/Sim3 are out of scope");
   CDV_REQUIRE(dtype == CDV_F32 || dtype == CDV_F64, CDV_ERR_UNSUPPORTED, "cdv_lie_op: dtype must be f32 or f64");
-  const bool binary = (op == OP_MUL || op == OP_ADJ || op == OP_ADJT || op == OP_ACT || op == OP_ACT4);
+  const bool binary = (op == OP_MUL || op == OP_ADJ || op == OP_ADJT || op == OP_ACT || op == OP_ACT4 || op == OP_JINV);
   CDV_REQUIRE(!binary || y != nullptr, CDV_ERR_ARG, "cdv_lie_op: binary op needs y");
   if (n == 0) return CDV_OK;
   hipStream_t s = (hipStream_t)stream;

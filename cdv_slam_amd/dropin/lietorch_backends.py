@@ -1,5 +1,7 @@
 """Drop-in for the reference's `lietorch_backends` extension (cdvslam/lietorch/src/lietorch.cpp:286-316).
-Forward ops of SO3 (group id 1) and SE3 (3); backward ops belong to the training path."""
+Forward and backward ops of SO3 (group id 1) and SE3 (3), `projector` and `Jinv`; one HIP launch each (csrc/lie.hip,
+lie_bwd.hip).  A group element's gradient is the left-perturbation row vector in the first K of its N words (DESIGN.md "The
+lietorch backward").  RxSO3 (2) and Sim3 (4) raise NotImplementedError."""
 from cdv_slam_amd import ops
 
 
@@ -39,20 +41,28 @@ def as_matrix(group_id, X):
     return ops.lie_op(group_id, "matrix", X)
 
 
-def _training_only(name):
-    def f(*args, **kwargs):
-        raise NotImplementedError("lietorch_backends.%s is the training path (out of scope)" % name)
-    f.__name__ = name
+def projector(group_id, X):
+    """[n, N, N]: the derivative of the stored row of Exp(eps) X by eps in the first K columns, the last column zero"""
+    return ops.lie_op(group_id, "projector", X)
+
+
+def Jinv(group_id, X, a):
+    """Jl^-1(Log X) a, [n, K]"""
+    return ops.lie_op(group_id, "Jinv", X, a)
+
+
+def _backward(op):
+    def f(group_id, grad, *inputs):
+        return [g for g in ops.lie_backward(group_id, op, grad, *inputs) if g is not None]
     return f
 
 
-expm_backward = _training_only("expm_backward")
-logm_backward = _training_only("logm_backward")
-inv_backward = _training_only("inv_backward")
-mul_backward = _training_only("mul_backward")
-adj_backward = _training_only("adj_backward")
-adjT_backward = _training_only("adjT_backward")
-act_backward = _training_only("act_backward")
-act4_backward = _training_only("act4_backward")
-projector = _training_only("projector")
-Jinv = _training_only("Jinv")
+# (group_id, grad, *inputs) -> the list of input gradients, as the reference's do: [da], [dX], [dX, dY], [dX, da], [dX, dp]
+expm_backward = _backward("exp")
+logm_backward = _backward("log")
+inv_backward = _backward("inv")
+mul_backward = _backward("mul")
+adj_backward = _backward("adj")
+adjT_backward = _backward("adjT")
+act_backward = _backward("act")
+act4_backward = _backward("act4")

@@ -1,4 +1,4 @@
-"""Lie-group value types over the HIP backend (cdv_slam_amd/csrc/lie.hip), forward only.
+"""Lie-group value types over the HIP backend (cdv_slam_amd/csrc/lie.hip forward, lie_bwd.hip backward).
 
 The operator surface the update path's callers use -- `SE3(data)`, `X * Y`, `X * points`, `X[:, idx]`, `.inv()`,
 `.log()`, `.retr(a)`, `.adjT(a)`, `.matrix()`, `SE3.exp(a)`, `SE3.Identity(...)`, `cat` / `stack` -- with the meaning
@@ -10,6 +10,14 @@ Own construction: a group is a row of `_SPECS` (id, tangent / embedded width); e
 `_LIE_OPS` (backend op, arity, whether the result is a group element) turned into a method by `_install_lie_ops`;
 tensor-like helpers are generated from `_DATA_PASSTHROUGH`.  Every operation is one launch of `cdv_lie_op` on flat
 contiguous rows; broadcasting is an `expand` view made contiguous once (no `repeat`).
+
+Autograd.  With grad mode on and an operand that requires grad, `exp, log, inv, mul, adj, adjT, act, act4` (hence `retr`,
+`translation`, `*`) run through `_LieFn`, whose backward is one launch of `cdv_lie_bwd`; otherwise a call is exactly the
+launches above.  The gradient that flows through a group element's `data` is the left-perturbation row vector (K words and
+a zero, DESIGN.md "The lietorch backward"); `vec()` / `InitFromVec` are where it meets an ordinary gradient, through the
+`projector`.  A broadcast in which one operand's trailing batch dimensions are all 1 (one pose against its points) hands
+that operand to the backward unexpanded, and the kernel sums its rows; any other broadcast is `expand` and torch's sum.
+`matrix` and `Jinv` have no backward.
 """
 
 import torch
@@ -38,15 +46,95 @@ def _rows(t):
     return t.reshape(-1, t.shape[-1]).contiguous()
 
 
+class _LieFn(torch.autograd.Function):
+    """one Lie op on flat rows with its backward.  rep = (rx, ry): the operand with r > 1 comes unexpanded ([n / r] rows,
+    each used r times) -- the forward expands it, the backward sums in the kernel"""
+
+    @staticmethod
+    def forward(ctx, gid, op, rep, x, y):
+        ctx.gid, ctx.op, ctx.rep = gid, op, rep
+        ctx.save_for_backward(x, y)
+        xe, ye = (t if t is None or r == 1 else t[:, None].expand(-1, r, -1).reshape(-1, t.shape[-1])
+                  for t, r in zip((x, y), rep))
+        return ops.lie_op(gid, op, xe) if y is None else ops.lie_op(gid, op, xe, ye)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        x, y = ctx.saved_tensors
+        dx, dy = ops.lie_backward(ctx.gid, ctx.op, grad.contiguous(), x, y, need=ctx.needs_input_grad[3:5], rep=ctx.rep)
+        return None, None, None, dx, dy
+
+
+class _VecFn(torch.autograd.Function):
+    """data <-> group element: the identity forward; backward through the projector P (group_ops.py:73-101 of the reference):
+    leaving the group (vec) grad P, entering it (InitFromVec) grad pinv(P)"""
+
+    @staticmethod
+    def forward(ctx, gid, entering, data):
+        ctx.gid, ctx.entering = gid, entering
+        ctx.save_for_backward(data)
+        return data.view_as(data)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        (data,) = ctx.saved_tensors
+        P = ops.lie_op(ctx.gid, "projector", _rows(data.detach()))
+        P = torch.linalg.pinv(P) if ctx.entering else P
+        g = torch.matmul(_rows(grad).unsqueeze(-2), P).squeeze(-2)
+        return None, None, g.view(data.shape)
+
+
+_HAS_BACKWARD = ("exp", "log", "inv", "mul", "adj", "adjT", "act", "act4")
+
+
+def _wants_grad(op, x, y):
+    return (op in _HAS_BACKWARD and torch.is_grad_enabled()
+            and (x.requires_grad or (y is not None and y.requires_grad)))
+
+
+def _trailing_repeat(a, b):
+    """m > 1 when a's trailing batch dimensions are all 1 where b's hold m elements, and the batches agree in front of them
+    (so that b is the broadcast shape and row i of it uses row i // m of a); else 0"""
+    sa, sb = a.shape[:-1], b.shape[:-1]
+    t = 0
+    while t < len(sa) and sa[len(sa) - 1 - t] == 1:
+        t += 1
+    while t > 0 and sa[:len(sa) - t] != sb[:len(sb) - t]:
+        t -= 1                                              # a leading 1 that b shares is not part of the repeat
+    m = 1
+    for d in sb[len(sb) - t:] if t else ():
+        m *= d
+    return m if m > 1 else 0
+
+
+def _launch_grad(gid, op, x, y):
+    """_launch through _LieFn"""
+    if y is None:
+        return _LieFn.apply(gid, op, (1, 1), _rows(x), None).view(tuple(x.shape[:-1]) + (-1,))
+    batch = tuple(torch.broadcast_shapes(x.shape[:-1], y.shape[:-1]))
+    mx, my = _trailing_repeat(x, y), _trailing_repeat(y, x)
+    if 0 < mx <= ops.LIE_BWD_MAX_REP:
+        out = _LieFn.apply(gid, op, (mx, 1), _rows(x), _rows(y))
+    elif 0 < my <= ops.LIE_BWD_MAX_REP:
+        out = _LieFn.apply(gid, op, (1, my), _rows(x), _rows(y))
+    else:
+        out = _LieFn.apply(gid, op, (1, 1), _rows(x.expand(batch + x.shape[-1:])), _rows(y.expand(batch + y.shape[-1:])))
+    return out.view(batch + (-1,))
+
+
 def _launch(gid, op, x, y=None):
     """one backend launch on broadcast batch dims; returns [batch..., out...]"""
+    if y is not None and x.dim() != y.dim():
+        raise ValueError("lietorch: operands need the same number of dimensions (got %s and %s)"
+                         % (tuple(x.shape), tuple(y.shape)))
+    if _wants_grad(op, x, y):
+        return _launch_grad(gid, op, x, y)
     if y is None:
         out = ops.lie_op(gid, op, _rows(x))
         batch = tuple(x.shape[:-1])
     else:
-        if x.dim() != y.dim():
-            raise ValueError("lietorch: operands need the same number of dimensions (got %s and %s)"
-                             % (tuple(x.shape), tuple(y.shape)))
         batch = tuple(torch.broadcast_shapes(x.shape[:-1], y.shape[:-1]))
         out = ops.lie_op(gid, op, _rows(x.expand(batch + x.shape[-1:])), _rows(y.expand(batch + y.shape[-1:])))
     return out.view(batch + tuple(out.shape[1:]))
@@ -74,6 +162,8 @@ class LieGroup:
     tangent_shape = property(lambda self: self.data.shape[:-1] + (self.manifold_dim,))
 
     def vec(self):
+        if torch.is_grad_enabled() and self.data.requires_grad:
+            return _VecFn.apply(self.group_id, False, self.data)
         return self.data
 
     # ---- construction -----------------------------------------------------------------------------------
@@ -90,6 +180,8 @@ class LieGroup:
 
     @classmethod
     def InitFromVec(cls, data):
+        if torch.is_grad_enabled() and data.requires_grad:
+            return cls(_VecFn.apply(cls.group_id, True, data))
         return cls(data)
 
     @classmethod
@@ -116,6 +208,10 @@ class LieGroup:
         origin = self.data.new_zeros((1,) * (self.data.dim() - 1) + (4,))
         origin[..., 3] = 1.0
         return _launch(self.group_id, "act4", self.data, origin)
+
+    def Jinv(self, a):
+        """Jl^-1(Log X) a (no backward)"""
+        return _launch(self.group_id, "Jinv", self.data, a)
 
     def quaternion(self):
         return self.data[..., -4:]

@@ -13,7 +13,8 @@ from . import _lib
 
 F16, F32, F64 = 0, 1, 2
 _DT = {torch.float16: F16, torch.float32: F32, torch.float64: F64}
-LIE_OPS = {"exp": 0, "log": 1, "inv": 2, "mul": 3, "adj": 4, "adjT": 5, "act": 6, "act4": 7, "matrix": 8}
+LIE_OPS = {"exp": 0, "log": 1, "inv": 2, "mul": 3, "adj": 4, "adjT": 5, "act": 6, "act4": 7, "matrix": 8,
+           "projector": 9, "Jinv": 10}
 
 # default index-range capacities of the graph workspace (reference buffers: BUFFER_SIZE = 4096 frames
 # x 96 patches, cdvslam/config.py, patchgraph.py:25-29)
@@ -1396,7 +1397,8 @@ def ba_forward(poses, patches, intrinsics, target, weight, lmbda, ii, jj, kk, PP
 # lietorch
 # ---------------------------------------------------------------------------------------------------
 
-_LIE_OUT = {"exp": "N", "log": "K", "inv": "N", "mul": "N", "adj": "K", "adjT": "K", "act": 3, "act4": 4, "matrix": 16}
+_LIE_OUT = {"exp": "N", "log": "K", "inv": "N", "mul": "N", "adj": "K", "adjT": "K", "act": 3, "act4": 4, "matrix": 16,
+            "projector": "NN", "Jinv": "K"}
 
 
 def lie_op(group_id, op, x, y=None):
@@ -1412,8 +1414,46 @@ def lie_op(group_id, op, x, y=None):
     N, K = (7, 6) if group_id == 3 else (4, 3)
     n = x.shape[0]
     od = _LIE_OUT[op]
-    od = N if od == "N" else K if od == "K" else od
+    od = N if od == "N" else K if od == "K" else N * N if od == "NN" else od
     z = torch.empty((n, od), dtype=x.dtype, device=x.device)
     rc = lib.cdv_lie_op(group_id, LIE_OPS[op], _DT[x.dtype], n, _p(x), _p(y), _p(z), _stream())
     _lib.check(rc, "cdv_lie_op")
-    return z.view(n, 4, 4) if op == "matrix" else z
+    return z.view(n, 4, 4) if op == "matrix" else z.view(n, N, N) if op == "projector" else z
+
+
+# the ops with a backward: number of inputs, and whether (input 0, input 1, output) are group elements
+_LIE_BWD = {"exp": 1, "log": 1, "inv": 1, "mul": 2, "adj": 2, "adjT": 2, "act": 2, "act4": 2}
+LIE_BWD_MAX_REP = 64
+
+
+def lie_backward(group_id, op, grad, x, y=None, need=(True, True), rep=(1, 1)):
+    """lietorch_backends.<op>_backward on flat contiguous rows (cdv_lie_bwd): grad [n, width of the op's output], x / y as
+    the forward takes them -> (dx | None, dy | None) shaped like x / y (dy is None for a unary op).  A group element's
+    gradient is the left-perturbation row vector in the first K of its N words, the last zero, and the incoming gradient
+    of a group-valued output is read the same way.  rep = (rx, ry): the operand with r > 1 (at most one, at most
+    LIE_BWD_MAX_REP) has n / r rows, row i uses its row i // r, and its gradient is the in-kernel sum of its r rows."""
+    lib = _lib.load()
+    _need_cuda(grad, x, y)
+    if x.dtype not in (torch.float32, torch.float64):
+        raise TypeError("lietorch ops: float32 or float64")
+    if grad.dtype != x.dtype or (y is not None and y.dtype != x.dtype):
+        raise TypeError("lietorch ops: one dtype per call")
+    if not (grad.is_contiguous() and x.is_contiguous() and (y is None or y.is_contiguous())):
+        raise RuntimeError("lietorch ops: inputs must be contiguous (lietorch.cpp:7)")
+    if group_id not in (1, 3):
+        raise NotImplementedError("only SO3 (1) and SE3 (3) are on the update path")
+    if op not in _LIE_BWD:
+        raise ValueError("lie_backward: %r has no backward" % (op,))
+    binary = _LIE_BWD[op] == 2
+    if binary and y is None:
+        raise ValueError("lie_backward: %s needs y" % op)
+    n, (rx, ry) = grad.shape[0], (int(rep[0]), int(rep[1]))
+    if x.shape[0] * rx != n or (binary and y.shape[0] * ry != n):
+        raise ValueError("lie_backward: rows of grad (%d) must be rows of x times rep[0] (and of y times rep[1])" % n)
+    need_x, need_y = bool(need[0]), binary and bool(need[1])
+    dx = torch.empty_like(x) if need_x else None
+    dy = torch.empty_like(y) if need_y else None
+    a = _lib.LieBwdArgs(group_id, LIE_OPS[op], _DT[x.dtype], int(need_x) | int(need_y) << 1, n, rx, ry if binary else 1,
+                        _p(grad), _p(x), _p(y) if binary else None, _p(dx), _p(dy))
+    _lib.check(lib.cdv_lie_bwd(ctypes.byref(a), _stream()), "cdv_lie_bwd")
+    return dx, dy

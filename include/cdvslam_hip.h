@@ -43,7 +43,7 @@
  *                 cdv_shadows_sync (fingerprinted as 32-bit words); net / net_out of cdv_edges_remove; the buffers of
  *                 cdv_frames_keyframe_shift (which picks 16- or 4-byte pieces by what the base allows)
  *     Everything else -- in particular every pointer of cdv_transform (a coords or intrinsics pointer that is not 16-byte
- *     aligned selects the lane-per-edge kernel, same values), cdv_fastba_reproject, cdv_flow_mag, cdv_point_cloud, cdv_lie_op,
+ *     aligned selects the lane-per-edge kernel, same values), cdv_fastba_reproject, cdv_flow_mag, cdv_point_cloud, cdv_lie_op, cdv_lie_bwd,
  *     cdv_corr_fwd, the patchify calls, the planar tile array and the index lists -- needs its element's alignment only: wide
  *     accesses to those go through types declared 4-byte aligned, which global memory takes.
  */
@@ -701,8 +701,33 @@ int cdv_stream_frame(cdv_stream_desc* desc, const void* fmap_chw, const float* c
  * lietorch forward ops  (replaces lietorch_backends.{expm,logm,inv,mul,adj,adjT,act,act4,as_matrix})
  * group ids as the reference: SO3 = 1, SE3 = 3 (lietorch.cpp:286-316, groups.py:236-290).
  * op: 0 exp, 1 log, 2 inv, 3 mul, 4 adj, 5 adjT, 6 act, 7 act4, 8 as_matrix.  Flat [n][dim] rows.
+ * Two more ops have the forward's shape and serve the backward's callers (N / K: embedded / tangent width):
+ *   9 projector: x = X -> z [n][N][N], column k < K the derivative of the stored row of Exp(eps) X by eps_k at 0, last column 0
+ *   10 Jinv:     x = X, y = a [n][K] -> z [n][K] = Jl^-1(Log X) a
  * ---------------------------------------------------------------------------------------------- */
 int cdv_lie_op(int group, int op, int dtype, int64_t n, const void* x, const void* y, void* z, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * lietorch backward ops  (replaces lietorch_backends.{expm,logm,inv,mul,adj,adjT,act,act4}_backward)
+ * The gradient with respect to a group element X is the row vector dL/d eps at eps = 0 of L(Exp(eps) X) in the first K
+ * words of an N-word row, the last word zero; the incoming gradient of a group-valued output is read the same way.  Tangent
+ * and point operands carry ordinary gradients.  Rows: grad [n][width of the op's output], x / y as the forward takes them,
+ * dx / dy shaped like x / y.
+ * One operand may be grouped (rep > 1, at most 64): it has n / rep rows, row i of the call uses its row i / rep, and its
+ * gradient comes back as [n / rep] rows, each the sum of its rep rows in ascending order (no float atomics: the same bits
+ * at every run).  The record is host memory and is read before the call returns; the call only enqueues on `stream`
+ * (capturable).  n == 0: CDV_OK, nothing is enqueued.
+ * Errors: CDV_ERR_UNSUPPORTED for a group other than 1 / 3 or a dtype other than f32 / f64; CDV_ERR_ARG for op 8 (as_matrix
+ * has no backward) or an unknown op, n not a multiple of a rep, both reps above 1, a rep above 64 or on a unary op, and a
+ * needed output that is NULL.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct cdv_lie_bwd_args {
+  int32_t group, op, dtype, need;    /* op: the forward op's code 0..7; need bit 0 / 1: first / second input's gradient */
+  int64_t n, rep_x, rep_y;           /* rows of grad; rows of x = n / rep_x, of y = n / rep_y; at most one of them > 1 */
+  const void *grad, *x, *y;          /* device */
+  void *dx, *dy;                     /* device; may be NULL when not needed */
+} cdv_lie_bwd_args;
+int cdv_lie_bwd(const cdv_lie_bwd_args* args, void* stream);
 
 #ifdef __cplusplus
 }
