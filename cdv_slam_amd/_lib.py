@@ -49,6 +49,8 @@ SIGNATURES = {
     "cdv_flow_mag": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _f32, _vp, _vp, _vp]),
     "cdv_point_cloud": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp]),
     "cdv_transform": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cdv_transform_bwd_workspace_bytes": (_sz, [_i64, _i64, _i64, _i32]),
+    "cdv_transform_bwd": (_i32, [_vp, _vp]),
     "cdv_fastba_reproject": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp]),
     "cdv_graph_workspace_bytes": (_sz, [_i64, _i64]),
     "cdv_graph_build": (_i32, [_vp, _vp, _i64, _vp, _sz, _i64, _i64, _vp]),
@@ -129,6 +131,13 @@ class LieBwdArgs(ctypes.Structure):
     _fields_ = ([(n, ctypes.c_int32) for n in ("group", "op", "dtype", "need")]
                 + [(n, ctypes.c_int64) for n in ("n", "rep_x", "rep_y")]
                 + [(n, ctypes.c_void_p) for n in ("grad", "x", "y", "dx", "dy")])
+
+
+class TransformBwdArgs(ctypes.Structure):
+    """cdv_transform_bwd_args (include/cdvslam_hip.h): one backward call of the fused transform, field for field"""
+    _fields_ = ([(n, ctypes.c_void_p) for n in ("poses", "patches", "intrinsics", "ii", "jj", "kk")]
+                + [(n, ctypes.c_int64) for n in ("E", "n", "m")] + [(n, ctypes.c_int32) for n in ("P", "flags")]
+                + [(n, ctypes.c_void_p) for n in ("grad_coords", "dposes", "dpatches", "workspace")])
 
 
 class ShadowRing(ctypes.Structure):

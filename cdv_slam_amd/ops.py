@@ -601,6 +601,64 @@ def transform(poses, patches, intrinsics, ii, jj, kk, layout_e2pp=False, valid=F
     return coords
 
 
+_tfb_ws = {}          # device -> the workspace of cdv_transform_bwd (grown as needed; its contents need no initialisation)
+
+
+def _tfb_workspace(dev, need):
+    ws = _tfb_ws.get(dev)
+    if ws is None or ws.numel() < need:
+        ws = _tfb_ws[dev] = torch.empty(int(need * 1.25) + 4096, dtype=torch.uint8, device=dev)
+    return ws
+
+
+def _grad_layout(grad, E, P):
+    """(tensor to pass, E2PP?) of a [1,E,P,P,2] gradient of any strides: a permuted view of a contiguous [1,E,2,P,P] buffer
+    (what the caller's `.permute(0, 1, 4, 2, 3).contiguous()` sends back) goes as E2PP and a contiguous tensor as EPP2, both
+    without a copy; anything else is made contiguous first"""
+    if grad.is_contiguous():
+        return grad, False
+    if E > 0 and grad.permute(0, 1, 4, 2, 3).is_contiguous():
+        return grad, True
+    return grad.contiguous(), False
+
+
+def transform_backward(poses, patches, intrinsics, ii, jj, kk, grad, need=(True, True), layout_e2pp=None):
+    """The vector-Jacobian product of `transform`'s coords (cdv_transform_bwd): poses [1,n,7], patches [1,m,3,P,P], intrinsics
+    [1,n,4] as the forward takes them, grad [1,E,P,P,2] of any strides (layout_e2pp=None), or a contiguous [1,E,2,P,P]
+    (layout_e2pp=True) / [1,E,P,P,2] (False) -> (dposes | None, dpatches | None) shaped like the inputs; `need` says which.
+    A pose row's gradient is the left-perturbation row vector in words 0..5, word 6 zero (as lie_backward).  Deterministic:
+    no float atomics, every word written once."""
+    lib = _lib.load()
+    _need_cuda(poses, patches, intrinsics, ii, jj, kk, grad)
+    for t, what in ((poses, "poses"), (patches, "patches"), (intrinsics, "intrinsics"), (grad, "grad")):
+        if t.dtype != torch.float32:
+            raise TypeError("cdv_transform_bwd is float32 (%s is %s)" % (what, t.dtype))
+    poses, patches, intrinsics = poses.contiguous(), patches.contiguous(), intrinsics.contiguous()
+    ii, jj, kk = ii.contiguous(), jj.contiguous(), kk.contiguous()
+    E, P = ii.numel(), patches.shape[-1]
+    n, m = poses.shape[-2], patches.shape[1]
+    if layout_e2pp is None:
+        if tuple(grad.shape) != (1, E, P, P, 2):
+            raise ValueError("transform_backward: grad must be [1,E,P,P,2] (got %s)" % (tuple(grad.shape),))
+        grad, e2pp = _grad_layout(grad, E, P)
+    else:
+        e2pp = bool(layout_e2pp)
+        if tuple(grad.shape) != ((1, E, 2, P, P) if e2pp else (1, E, P, P, 2)):
+            raise ValueError("transform_backward: grad does not have the shape of its layout (got %s)" % (tuple(grad.shape),))
+        grad = grad.contiguous()
+    need_poses, need_patches = bool(need[0]), bool(need[1])
+    dev = poses.device
+    dposes = torch.empty(poses.shape, dtype=torch.float32, device=dev) if need_poses else None
+    dpatches = torch.empty(patches.shape, dtype=torch.float32, device=dev) if need_patches else None
+    if not (need_poses or need_patches):
+        return None, None
+    ws = _tfb_workspace(dev, int(lib.cdv_transform_bwd_workspace_bytes(E, n, m, P))) if E > 0 else None
+    a = _lib.TransformBwdArgs(_p(poses), _p(patches), _p(intrinsics), _p(ii), _p(jj), _p(kk), E, n, m, P, 1 if e2pp else 0,
+                              _p(grad), _p(dposes), _p(dpatches), _p(ws))
+    _lib.check(lib.cdv_transform_bwd(ctypes.byref(a), _stream()), "cdv_transform_bwd")
+    return dposes, dpatches
+
+
 def fastba_reproject(poses, patches, intrinsics, ii, jj, kk):
     """cuda_ba.reproject (ba_cuda.cu:408-458, 614-646) -> [1,E,2,P,P]."""
     lib = _lib.load()

@@ -5,6 +5,18 @@
 elementwise ops (projective_ops.py:53-130).  The kernels serve what the update path hands them -- float32 state, batch
 1, SE3 poses -- and anything else raises: there is no composed fallback.  `iproj` / `proj` are the two pinhole maps as
 plain tensor expressions for callers that want them on their own.
+
+Autograd.  With grad mode on and poses (the tensor, or a group object's `.data`) or patches that require grad, `transform`
+runs through `_TransformFn`: the forward is the same launch (`ops.transform`, the same bits, the same permuted view of an
+E2PP buffer), the backward is `ops.transform_backward` (csrc/transform_bwd.hip) -- the pose gradient is the
+left-perturbation row vector the Lie classes and the reference's GroupOps exchange.  Otherwise a call is exactly the code
+path without autograd, the compiled lane included.  The intrinsics carry no gradient and `tonly=True` has no backward
+(NotImplementedError for both).  ONE branch is composed instead of fused: `jacobian=True` under grad (the reference's ba.py
+reaches it from its second iteration on with poses that require grad).  There the coordinates and `valid` still come from
+the fused Function, but the Jacobians carry gradient in the reference and there are no fused second derivatives here, so
+(Ji, Jj, Jz) are built by `_jacobians_composed` from this package's differentiable Lie classes with the reference's formulas
+(projective_ops.py:71-106).  `reproject`, `flow_mag` and `point_cloud` are inference only: they return tensors without a
+graph.
 """
 import torch
 
@@ -53,13 +65,85 @@ def _kernel_pose_rows(poses, what):
     return data
 
 
+class _TransformFn(torch.autograd.Function):
+    """coords [1,E,P,P,2] (and the per-pixel validity mask) of the fused transform with the fused backward: the launches and
+    the layouts of the call without autograd"""
+
+    @staticmethod
+    def forward(ctx, data, patches, intrinsics, ii, jj, kk, valid):
+        ctx.save_for_backward(data, patches, intrinsics, ii, jj, kk)
+        if valid:
+            coords, mask = ops.transform(data, patches, intrinsics, ii, jj, kk, layout_e2pp=False, valid=True)
+            ctx.mark_non_differentiable(mask)
+            return coords, mask
+        return ops.transform(data, patches, intrinsics, ii, jj, kk, layout_e2pp=True).permute(0, 1, 3, 4, 2), None
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad, _grad_mask):
+        data, patches, intrinsics, ii, jj, kk = ctx.saved_tensors
+        # what comes back through the caller's `.permute(0, 1, 4, 2, 3).contiguous()` is a permuted view of a contiguous
+        # [1,E,2,P,P] buffer: transform_backward reads it where it lies
+        dposes, dpatches = ops.transform_backward(data, patches, intrinsics, ii, jj, kk, grad, need=ctx.needs_input_grad[0:2])
+        return dposes, dpatches, None, None, None, None, None
+
+
+def _jacobians_composed(poses, patches, intrinsics, ii, jj, kk):
+    """(Ji, Jj, Jz) of the reference's formulas (projective_ops.py:71-106) over this package's differentiable Lie classes, in
+    the dtype of its inputs (a float64 run of this function is the truth of its float32 run).  poses: an SE3 of this
+    package.  The last column of Gij.matrix() is Gij * (0, 0, 0, 1) (act4): as_matrix has no backward here."""
+    P = patches.shape[-1]
+    c = P // 2
+    Gij = poses[:, jj] * poses[:, ii].inv()
+    X0 = iproj(patches[:, kk][..., c:c + 1, c:c + 1], intrinsics[:, ii])[:, :, 0, 0]          # the centre pixel, [1,E,4]
+    X, Y, Z, H = (Gij * X0).unbind(dim=-1)
+    o = torch.zeros_like(H)
+    fx, fy, _, _ = intrinsics[:, jj].unbind(dim=-1)
+    far = Z.abs() > 0.2
+    d = torch.where(far, 1.0 / torch.where(far, Z, torch.ones_like(Z)), o)
+    Ja = torch.stack([H, o, o, o, Z, -Y,
+                      o, H, o, -Z, o, X,
+                      o, o, H, Y, -X, o,
+                      o, o, o, o, o, o], dim=-1).view(1, len(ii), 4, 6)
+    Jp = torch.stack([fx * d, o, -fx * X * d * d, o,
+                      o, fy * d, -fy * Y * d * d, o], dim=-1).view(1, len(ii), 2, 4)
+    Jj = torch.matmul(Jp, Ja)
+    Ji = -Gij[:, :, None].adjT(Jj)
+    e4 = torch.zeros_like(X0)
+    e4[..., 3] = 1.0
+    Jz = torch.matmul(Jp, (Gij * e4)[..., None])
+    return Ji, Jj, Jz
+
+
+def _transform_grad(poses, data, patches, intrinsics, ii, jj, kk, valid, jacobian, tonly):
+    """transform under autograd (module docstring)"""
+    if intrinsics.requires_grad:
+        raise NotImplementedError("transform: the intrinsics carry no gradient (not built)")
+    if tonly:
+        raise NotImplementedError("transform(tonly=True) has no backward (not built)")
+    _kernel_pose_rows(poses, "transform")
+    if patches.dtype != torch.float32:
+        raise NotImplementedError("transform: the HIP path serves float32 patches (got %s)" % patches.dtype)
+    coords, mask = _TransformFn.apply(data, patches, intrinsics, ii, jj, kk, bool(valid or jacobian))
+    if jacobian:
+        from .lietorch import SE3
+        c = patches.shape[-1] // 2
+        return coords, mask[:, :, c, c], _jacobians_composed(SE3(data), patches, intrinsics, ii, jj, kk)
+    return (coords, mask) if valid else coords
+
+
 def transform(poses, patches, intrinsics, ii, jj, kk, depth=False, valid=False, jacobian=False, tonly=False):
     """patch k of frame i seen from frame j (projective_ops.py:53-113), one launch.
 
     -> coords [1,E,P,P,2]; valid=True: also (Z > 0.2) per pixel [1,E,P,P]; jacobian=True:
-    (coords, (Z > 0.2) at the centre [1,E], (Ji [1,E,2,6], Jj [1,E,2,6], Jz [1,E,2,1]))."""
+    (coords, (Z > 0.2) at the centre [1,E], (Ji [1,E,2,6], Jj [1,E,2,6], Jz [1,E,2,1])).  Differentiable by poses and
+    patches (module docstring)."""
     if depth:
         raise NotImplementedError("transform(depth=True) is not on the update path")
+    if torch.is_grad_enabled():
+        data = poses if torch.is_tensor(poses) else getattr(poses, "data", None)
+        if (torch.is_tensor(data) and data.requires_grad) or patches.requires_grad:
+            return _transform_grad(poses, data, patches, intrinsics, ii, jj, kk, valid, jacobian, tonly)
     if not (valid or jacobian or tonly) and ops._fast and ops._env("CDV_DROPIN_FAST", "1") != "0":
         # the compiled lane (csrc/dropin_fast.cpp): the same checks, allocation and launch as below without the Python around them
         group = not torch.is_tensor(poses)

@@ -43,7 +43,7 @@
  *                 cdv_shadows_sync (fingerprinted as 32-bit words); net / net_out of cdv_edges_remove; the buffers of
  *                 cdv_frames_keyframe_shift (which picks 16- or 4-byte pieces by what the base allows)
  *     Everything else -- in particular every pointer of cdv_transform (a coords or intrinsics pointer that is not 16-byte
- *     aligned selects the lane-per-edge kernel, same values), cdv_fastba_reproject, cdv_flow_mag, cdv_point_cloud, cdv_lie_op, cdv_lie_bwd,
+ *     aligned selects the lane-per-edge kernel, same values), cdv_transform_bwd (its workspace apart: 16 bytes), cdv_fastba_reproject, cdv_flow_mag, cdv_point_cloud, cdv_lie_op, cdv_lie_bwd,
  *     cdv_corr_fwd, the patchify calls, the planar tile array and the index lists -- needs its element's alignment only: wide
  *     accesses to those go through types declared 4-byte aligned, which global memory takes.
  */
@@ -271,6 +271,40 @@ int cdv_patchify_bwd(const void* patch_grad, const float* coords, void* net_grad
 int cdv_transform(const float* poses, const float* patches, const float* intrinsics, const int64_t* ii,
                   const int64_t* jj, const int64_t* kk, int64_t E, int P, int flags, float* coords, float* validpx,
                   float* valid, float* Ji, float* Jj, float* Jz, void* stream);
+
+/*
+ * The vector-Jacobian product of cdv_transform's coords by poses and patches (what autograd makes of projective_ops.py:53-69:
+ * iproj 19-29, the gathers, lietorch Inv / Mul / Act4 59-66, proj 32-50), f32.  The forward is recomputed from the inputs;
+ * quaternions are re-normalised on every load as in cdv_transform.  Per edge e (i, j, k = ii, jj, kk[e]; G = Gj Gi^-1) and
+ * pixel with incoming gradient (gu, gv):  X1 = G X0,  D = 1 / max(Z, 0.1),
+ *   q = (fx_j D gu, fy_j D gv, -[Z >= 0.1] D^2 (fx_j X gu + fy_j Y gv), 0)      (the clamp passes no gradient below 0.1)
+ *   a_e = sum over pixels of q [[X1_w I, -[X1_xyz]x], [0]];   dposes[j] += a_e;   dposes[i] += -a_e Ad(G)
+ *   dX0 = q M(G);   dpatches[k][0][p] += dX0_x / fx_i,  [1][p] += dX0_y / fy_i,  [2][p] += dX0_w
+ * A pose row's gradient is the left-perturbation row vector (dL / d eps at 0 of L(Exp(eps) X)) in words 0..5, word 6 zero, as
+ * cdv_lie_bwd has it.
+ *   grad_coords [E][P][P][2] or [E][2][P][P] by flags (CDV_TF_LAYOUT_*); dposes [n][7], dpatches [m][3][P][P]: either may be
+ *   NULL (not computed).  EVERY word of a requested output is written once (no zero-fill by the caller; a frame or patch
+ *   without an edge gets exact zeros).  No float atomics: one owner per output word and a summation order that depends on E,
+ *   n and the contents of ii / jj / kk only -- the same bits at every run, and a single-output call gives the bits of the
+ *   corresponding half of the two-output call.  An edge whose ii / jj / kk lies outside [0, n) / [0, m) contributes nothing.
+ *   The record is host memory and is read before the call returns.  Enqueue only (capturable): no host synchronisation.  workspace: cdv_transform_bwd_workspace_bytes(E, n, m, P) bytes,
+ *   16-byte aligned, contents need no initialisation (its integer counters are zeroed inside the call).
+ * Alignment: the element's only for every tensor (as cdv_transform); 16 bytes for the workspace.
+ * Errors: CDV_ERR_UNSUPPORTED for P other than 1 / 3, for CDV_TF_TONLY, and for dposes with n > 1024 (one LDS row per frame);
+ * CDV_ERR_ARG for a NULL workspace or input with E > 0.  E == 0: zeros to the requested outputs, CDV_OK (workspace may be
+ * NULL).
+ */
+size_t cdv_transform_bwd_workspace_bytes(int64_t E, int64_t n, int64_t m, int P);
+typedef struct cdv_transform_bwd_args {
+  const float *poses, *patches, *intrinsics;   /* device: [n][7], [m][3][P][P], [n][4] */
+  const int64_t *ii, *jj, *kk;                 /* device: [E] */
+  int64_t E, n, m;
+  int32_t P, flags;                            /* flags: CDV_TF_LAYOUT_EPP2 / _E2PP, the layout of grad_coords */
+  const float* grad_coords;                    /* device: [E][P][P][2] or [E][2][P][P] */
+  float *dposes, *dpatches;                    /* device: [n][7], [m][3][P][P]; NULL: not computed */
+  void* workspace;                             /* device */
+} cdv_transform_bwd_args;
+int cdv_transform_bwd(const cdv_transform_bwd_args* args, void* stream);
 
 /* cuda_ba.reproject (ba.cpp:50-57, ba_cuda.cu:408-458): intrinsics row 0, no depth clamp, no
  * quaternion normalisation -> coords [E][2][P][P] */
